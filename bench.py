@@ -13,8 +13,11 @@ include every broadcast and gather; up to three calls are in flight, so a call's
 at N = 1) overlaps the next calls' searches before its gather; value = n_ranges / max-over-ranks step time.  N = 1
 is the same path with no collective (compress_device), so the driver's per-N values form a strong-scaling curve.
 
-Also reported: the dominant kernel's roofline (similarity top-K vs the fp16 MFMA peak; HIP events on the launch
-stream; `traffic` = PMC bytes from a committed rocprofv3 pass of the same config, labelled with its source), the
+A plain run does only that: set up, warm up, time the steps, write the outputs (--dump-outputs) and print the result
+line.  Everything below runs behind --full.
+
+With --full also reported: the dominant kernel's roofline (similarity top-K vs the fp16 MFMA peak; HIP events on the
+launch stream; `traffic` = PMC bytes from a committed rocprofv3 pass of the same config, labelled with its source), the
 affine solver's HBM roofline measured on a pool above the 256 MB MALL (the north star's ≥60 % target), per-stage
 times, the decode (default and forced 50 iterations) and the CPU baseline (oracle restatement on this host,
 bounded sample, rank 0 at N=1 only).
@@ -49,8 +52,15 @@ def parse():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", default="cfg2")
     ap.add_argument("--seconds", type=float, default=None, help="override signal length (debug)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="only the timed steps (profiling passes)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything else the line can report: the search's roofline "
+                         "(re-timed alone), host-boundary and API rates, decode, ties, .fwav I/O, the affine solver's HBM "
+                         "roofline, the CPU baseline, and at N > 1 the per-rank phase breakdown")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (match arrays, domain pool) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: only the timed steps and the search's roofline (profiling passes)")
     ap.add_argument("--cpu-workers", default=None, help="CPU baseline search processes (default: sweep)")
     ap.add_argument("--tie-order", default="numpy",
                     help="compress_device tie_order (diagnostic: 'index' drops the host ranking of exactly tied rows, "
@@ -58,7 +68,10 @@ def parse():
     ap.add_argument("--streams", type=int, default=2,
                     help="HIP streams that consecutive timed calls alternate over (a call's kernels stay on one); "
                          "the same default at every N, so that the driver's 1 -> N curve compares like with like")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def pmc_traffic(config: str):
@@ -199,6 +212,34 @@ def fwav_io_bench() -> dict:
             "note": "cfg4 shape, seeded random values; one SHA-256 stream over the body bounds both directions"}
 
 
+DUMP_BYTES = 24 << 20  # --dump-outputs writes at most this much of the match arrays, and as much of the pool
+
+
+def _dump_rows(n: int, row_bytes: int) -> np.ndarray:
+    """All n rows if they fit DUMP_BYTES, else a seeded sample of them in ascending order (the same for every run)."""
+    if n * row_bytes <= DUMP_BYTES:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(0).integers(0, n, DUMP_BYTES // row_bytes))
+
+
+def dump_outputs(path: str, out: dict, rs: int) -> None:
+    """--dump-outputs: the arrays a caller of the timed path receives, from its last timed call, as <name>.npy: the
+    match arrays (idx as float64: a cfg4 index does not fit float32's 24 bits; s, o, sym, err as float32) and the
+    domain pool, one row per domain.  Of what is larger than DUMP_BYTES a seeded sample of rows is written; the row
+    numbers are in match_rows.npy and pool_rows.npy (float64)."""
+    os.makedirs(path, exist_ok=True)
+    names = (("idx", np.float64), ("s", np.float32), ("o", np.float32), ("sym", np.float32), ("err", np.float32))
+    rows = _dump_rows(out["idx"].numel(), sum(np.dtype(dt).itemsize for _, dt in names))
+    for name, dt in names:
+        np.save(os.path.join(path, name + ".npy"), out[name].cpu().numpy()[rows].astype(dt))
+    np.save(os.path.join(path, "match_rows.npy"), rows.astype(np.float64))
+    pool = out["pool"].reshape(-1, rs)
+    rows = _dump_rows(pool.shape[0], 4 * rs)
+    sample = pool.index_select(0, torch.from_numpy(rows).to(pool.device))
+    np.save(os.path.join(path, "pool.npy"), sample.cpu().numpy().astype(np.float32))
+    np.save(os.path.join(path, "pool_rows.npy"), rows.astype(np.float64))
+
+
 def main():
     args = parse()
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -219,8 +260,16 @@ def main():
             dist.init_process_group("nccl", device_id=torch.device("cuda", dev_index))
         else:
             dist.init_process_group(backend)
-    import __graft_entry__
-    __graft_entry__.build()
+    # A library built from these sources is used as it is, so the tree may be read-only (fwav._lib refuses a missing
+    # or stale one by its embedded source digest); only then is it built here.
+    from fwav import _lib
+    try:
+        _lib.product_lib()
+        if args.full:
+            _lib.debug_lib()  # the affine roofline's gather-only ceiling
+    except _lib.FwavError:
+        import __graft_entry__
+        __graft_entry__.build()
     from fwav import api, engine, synth
     from fwav import dist as fdist
 
@@ -328,15 +377,22 @@ def main():
     stage_ms = {s: float(np.mean([e[s][0].elapsed_time(e[s][1]) for e in evs])) for s in STAGES if s in evs[0]}
     n_active = int(res.n_active.item())
     nr, nd, rs = res.n_ranges, res.n_domains, res.range_size
+    if args.dump_outputs and rank == 0:
+        last = step.out if sharded else res
+        if sharded and last.get("empty"):
+            raise SystemExit("--dump-outputs: the signal has no ranges to match")
+        dump_outputs(args.dump_outputs, last if sharded else {k_: getattr(last, k_) for k_ in
+                                                              ("idx", "s", "o", "sym", "err", "pool")}, rs)
     per_rank = None
     if dist is not None:
-        for _ in range(3):  # phase breakdown (untimed)
-            step(phases=True)
-        torch.cuda.synchronize()
         cd = dev if backend == "nccl" else torch.device("cpu")
         t = torch.tensor([dt], dtype=torch.float64, device=cd)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if dist is not None and args.full:
+        for _ in range(3):  # phase breakdown (untimed)
+            step(phases=True)
+        torch.cuda.synchronize()
         mine = torch.tensor([stage_ms.get("sim_topk", 0.0), float(n_active), res.shard[1] - res.shard[0],
                              *[float(np.mean(phase.get(k_, [0.0]))) * 1e3 for k_ in ("broadcast_s", "compute_s",
                                                                                       "gather_s")]],
@@ -348,27 +404,6 @@ def main():
     ms = dt / args.steps * 1e3
     value = nr / (dt / args.steps)
 
-    # the roofline's launch time: with several streams the timed launches overlap (each one's HIP-event span includes
-    # the other stream's work), so the search is re-timed alone, on one stream, over untimed extra calls of the same
-    # shard (its kernels and outputs are those of the timed calls)
-    solo_ms = None
-    if len(streams) > 1:
-        s_loc = sig if not sharded else getattr(step, "sig_local", None)
-        if s_loc is not None:
-            solo = []
-            for i in range(6):
-                ev = {}
-                r_ = engine.compress_device(s_loc, tile, K, energy_thresh=1e-4, shard=res.shard if sharded else None,
-                                            events=ev, defer_ties=True)
-                r_.wait()
-                torch.cuda.synchronize()
-                if i:
-                    solo.append(ev["sim_topk"][0].elapsed_time(ev["sim_topk"][1]))
-            solo_ms = float(sorted(solo)[len(solo) // 2])
-    t_topk = (solo_ms if solo_ms is not None else stage_ms["sim_topk"]) * 1e-3
-    flops = 2.0 * n_active * nd * 16
-    achieved_tf = flops / t_topk / 1e12
-    traffic, traffic_src = pmc_traffic(args.config) if not sharded else (None, None)
     line = {
         "metric": "ranges matched/sec at tile_size=2048, top-K=64",
         "value": value, "unit": "ranges/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -382,39 +417,63 @@ def main():
                    "parallelism": "single GPU" if not sharded else f"ranges sharded x{world} (RCCL broadcast + "
                                                                   f"gather)",
                    "streams": len(streams)},
-        "roofline": {"kernel": f"{TOPK_KERNEL} (fp16 MFMA similarity GEMM pre-filter + streaming exact top-K)",
-                     "bound": "mfma", "achieved": achieved_tf, "peak": F16_MFMA_PEAK_TF, "unit": "TFLOP/s",
-                     "frac": achieved_tf / F16_MFMA_PEAK_TF, "traffic": traffic, "traffic_source": traffic_src,
-                     "work_per_launch": f"2*{n_active}*{nd}*16 = {flops:.4g} flop: the ALGORITHMIC work of the "
-                                        f"reference's scores (every query-domain pair, fractal.py:537). The kernel "
-                                        f"does not execute it all: a centroid bound skips the (tile, query set) pairs "
-                                        f"that cannot reach a member's band, so `frac` is an effective rate; the "
-                                        f"MFMA work actually executed is `mfma_executed`",
-                     "launch_ms": t_topk * 1e3, "rank": rank,
-                     **({"launch_ms_overlapped": stage_ms["sim_topk"],
-                         "note": f"{len(streams)} streams in the timed steps: their launches overlap, so launch_ms is "
-                                 "the same search timed alone on one stream (median of 5 extra calls); "
-                                 "launch_ms_overlapped is the timed launches' own span"} if solo_ms is not None else {})},
         "stage_ms": stage_ms,
     }
-    sq = sq_summary(args.config) if not sharded else None
-    if sq and sq.get("mfma_executed_flop_per_launch"):
-        ex_tf = sq["mfma_executed_flop_per_launch"] / t_topk / 1e12
-        line["roofline"]["mfma_executed"] = {
-            "flop_per_launch": sq["mfma_executed_flop_per_launch"], "achieved": ex_tf, "unit": "TFLOP/s",
-            "frac": ex_tf / F16_MFMA_PEAK_TF, "mfma_busy": sq.get("mfma_busy_frac"),
-            "wave_time": sq.get("wave_time"),
-            "note": "SQ_INSTS_MFMA x 32,768 flop (v_mfma_f32_32x32x16_f16) from the committed SQ pass of this config, "
-                    "over this run's launch time; mfma_busy = SQ_VALU_MFMA_BUSY_CYCLES / SIMD cycles",
-            "source": f"profiles/sq_{args.config}.json ({sq.get('source')})"}
-    if traffic:
-        # the north star's "fraction of the HBM roofline" for the same launch: measured HBM bytes (PMC) over its time
-        # (the kernel is bound by MFMA/VALU issue, not by HBM: its table is re-read from the Infinity Cache)
-        hbm = traffic / t_topk / 1e9
-        line["roofline"]["hbm"] = {"achieved": hbm, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": hbm / HBM_PEAK_GBS}
+    if args.full:
+        # the roofline's launch time: with several streams the timed launches overlap (each one's HIP-event span
+        # includes the other stream's work), so the search is re-timed alone, on one stream, over untimed extra calls of
+        # the same shard (its kernels and outputs are those of the timed calls)
+        solo_ms = None
+        s_loc = sig if not sharded else getattr(step, "sig_local", None)
+        if len(streams) > 1 and s_loc is not None:
+            solo = []
+            for i in range(6):
+                ev = {}
+                r_ = engine.compress_device(s_loc, tile, K, energy_thresh=1e-4, events=ev, defer_ties=True,
+                                            shard=res.shard if sharded else None)
+                r_.wait()
+                torch.cuda.synchronize()
+                if i:
+                    solo.append(ev["sim_topk"][0].elapsed_time(ev["sim_topk"][1]))
+            solo_ms = float(sorted(solo)[len(solo) // 2])
+        t_topk = (solo_ms if solo_ms is not None else stage_ms["sim_topk"]) * 1e-3
+        flops = 2.0 * n_active * nd * 16
+        achieved_tf = flops / t_topk / 1e12
+        traffic, traffic_src = pmc_traffic(args.config) if not sharded else (None, None)
+        work = (f"2*{n_active}*{nd}*16 = {flops:.4g} flop: the ALGORITHMIC work of the reference's scores (every "
+                f"query-domain pair, fractal.py:537). The kernel does not execute it all: a centroid bound skips the "
+                f"(tile, query set) pairs that cannot reach a member's band, so `frac` is an effective rate; the MFMA "
+                f"work actually executed is `mfma_executed`")
+        line["roofline"] = {
+            "kernel": f"{TOPK_KERNEL} (fp16 MFMA similarity GEMM pre-filter + streaming exact top-K)",
+            "bound": "mfma", "achieved": achieved_tf, "peak": F16_MFMA_PEAK_TF, "unit": "TFLOP/s",
+            "frac": achieved_tf / F16_MFMA_PEAK_TF, "traffic": traffic, "traffic_source": traffic_src,
+            "work_per_launch": work, "launch_ms": t_topk * 1e3, "rank": rank}
+        if solo_ms is not None:
+            line["roofline"].update({
+                "launch_ms_overlapped": stage_ms["sim_topk"],
+                "note": f"{len(streams)} streams in the timed steps: their launches overlap, so launch_ms is the same "
+                        "search timed alone on one stream (median of 5 extra calls); launch_ms_overlapped is the timed "
+                        "launches' own span"})
+        sq = sq_summary(args.config) if not sharded else None
+        if sq and sq.get("mfma_executed_flop_per_launch"):
+            ex_tf = sq["mfma_executed_flop_per_launch"] / t_topk / 1e12
+            line["roofline"]["mfma_executed"] = {
+                "flop_per_launch": sq["mfma_executed_flop_per_launch"], "achieved": ex_tf, "unit": "TFLOP/s",
+                "frac": ex_tf / F16_MFMA_PEAK_TF, "mfma_busy": sq.get("mfma_busy_frac"),
+                "wave_time": sq.get("wave_time"),
+                "note": "SQ_INSTS_MFMA x 32,768 flop (v_mfma_f32_32x32x16_f16) from the committed SQ pass of this "
+                        "config, over this run's launch time; mfma_busy = SQ_VALU_MFMA_BUSY_CYCLES / SIMD cycles",
+                "source": f"profiles/sq_{args.config}.json ({sq.get('source')})"}
+        if traffic:
+            # the north star's "fraction of the HBM roofline" for the same launch: measured HBM bytes (PMC) over its
+            # time (the kernel is bound by MFMA/VALU issue, not by HBM: its table is re-read from the Infinity Cache)
+            hbm = traffic / t_topk / 1e9
+            line["roofline"]["hbm"] = {"achieved": hbm, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                                       "frac": hbm / HBM_PEAK_GBS}
     if per_rank is not None:
         line["per_rank"] = per_rank
-    extras = not sharded and not args.no_extras
+    extras = args.full and not sharded and not args.no_extras
     if extras:
         # Host-boundary rate (not `value`): numpy signal in host memory → matches (SoA) back in host memory.
         def e2e_step():
