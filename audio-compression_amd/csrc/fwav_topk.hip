@@ -34,6 +34,7 @@
 #include <algorithm>
 #include <cstring>
 #include <type_traits>
+#include "fwav_centroid_bound.h"
 #include "fwav_common.h"
 #include "../../include/fwav.h"
 
@@ -1422,10 +1423,11 @@ __device__ __forceinline__ uint64_t cent_set_mask(int s) {
   return m << s;
 }
 // The lane's centroid (column col = lane & 31, half h = lane >> 5): the fp16 mean of its members' query fragments and
-// the slack (ρ_0 + ρ_1)(1 + 2⁻⁹) + 1e-5 added to every member bound.  `qrow_of(k)` = member k's table row, or −1.
+// the constants of its filter threshold (fwav_centroid_bound.h: the worst-case slack (ρ_0 + ρ_1)(1 + 2⁻⁹) + 1e-5 and
+// the score-dependent bound's Γ·D + η, 2σ²D², σ²/N²).  `qrow_of(k)` = member k's table row, or −1.
 template <int QS, class RowOf>
 __device__ __forceinline__ void centroid_setup(const _Float16* __restrict__ emb16, RowOf qrow_of, half8& bc,
-                                               float& slack) {
+                                               CentBound& cb) {
   typedef float floatx8 __attribute__((ext_vector_type(8)));
   const int lane = threadIdx.x & 63;
   const int h = lane >> 5;
@@ -1445,31 +1447,35 @@ __device__ __forceinline__ void centroid_setup(const _Float16* __restrict__ emb1
     }
   }
   half8 c;
+  float cf[8];
 #pragma unroll
-  for (int i = 0; i < 8; ++i) c[i] = (_Float16)(nv > 0 ? sum[i] / (float)nv : 0.0f);
-  float rho = 0.0f;
+  for (int i = 0; i < 8; ++i) {
+    c[i] = (_Float16)(nv > 0 ? sum[i] / (float)nv : 0.0f);
+    cf[i] = (float)c[i];
+  }
+  CentHead own;  // this lane's head ...
+  cent_head_begin(own, cf);
 #pragma unroll
   for (int k = 0; k < QS; ++k) {
     const int64_t r = qrow_of(k);
     if (r >= 0) {
       const half8 m = frag(r);
-      float d2 = 0.0f;
+      float mf[8];
 #pragma unroll
-      for (int i = 0; i < 8; ++i) {
-        const float d = (float)m[i] - (float)c[i];  // exact: a difference of two fp16 values
-        d2 += d * d;
-      }
-      rho = fmaxf(rho, __builtin_sqrtf(d2));
+      for (int i = 0; i < 8; ++i) mf[i] = (float)m[i];
+      cent_head_member(own, cf, mf);
     }
   }
-  rho += __shfl_xor(rho, 32);  // both heads
+  // ... and the other one's (the constants are symmetric in the heads: both lanes of a column get the same)
+  const CentHead oth{__shfl_xor(own.n2, 32), __shfl_xor(own.rho, 32), __shfl_xor(own.beta, 32),
+                     __shfl_xor(own.perp2, 32)};
   bc = c;
-  slack = rho * (1.0f + 0x1p-9f) + 1e-5f;
+  cb = cent_bound(own, oth);
 }
-// The lane's centroid filter threshold: the smallest stream threshold (float) of its members minus the slack
-// (+∞ when no member takes appends; −∞ members make the centroid fire on every tile).
+// The lane's centroid filter threshold from the smallest stream threshold (float) of its members (+∞ when no member
+// takes appends; −∞ members make the centroid fire on every tile).  `tight` = false: the worst-case slack alone.
 template <int QS>
-__device__ __forceinline__ int centroid_threshold(const float (&tv)[QS], float slack) {
+__device__ __forceinline__ int centroid_threshold(const float (&tv)[QS], const CentBound& cb, bool tight) {
   const int lane = threadIdx.x & 63;
   const int col = lane & 31;
   const int sj = col % QS, base = (lane & 32) + QS * (col / QS);
@@ -1484,7 +1490,7 @@ __device__ __forceinline__ int centroid_threshold(const float (&tv)[QS], float s
     }
     mn = fminf(mn, v);
   }
-  return int_threshold(mn - slack);
+  return int_threshold(cent_threshold(cb, mn, tight));
 }
 // Level 1 of the centroid pre-filter over one group of NC chunks: the 32 centroids scored against every tile (the
 // stream's software pipeline: fragments 3 tiles ahead, MFMAs one tile ahead); pend[s] bit i marks tile i of the group
@@ -1598,7 +1604,8 @@ __global__ __launch_bounds__(64 * W, MODE == kModeEX ? FWAV_TOPK_EXWPE : (CENT ?
   // dbg (STATS builds only; timing ablations, outputs invalid): 1 = never take the slow path,
   // 2 = skip MFMA + threshold test, 4 = no global chunk loads, 128 = DMA only every other chunk,
   // 256 = no group barrier, 512 = fold without ballots, 1024 = MFMA without fold, 4096 = record the workgroup
-  // timeline (combinable with the others), 8192 = no seeded band limits
+  // timeline (combinable with the others), 8192 = no seeded band limits; 2048 = the centroid filter with its
+  // worst-case slack alone (outputs valid: the A/B of the score-dependent bound)
   if (!STATS) dbg = FWAV_TOPK_ABL;  // production: 0; ablation builds (-DFWAV_TOPK_ABL=bits) fix the bits at compile time
   half8 b[QS], bl[QS];  // the query's fp16 high and low parts (MFMA B operands)
   float thf[QS];        // band limit: on shl (first pass), on s16 (exact mode)
@@ -1671,7 +1678,7 @@ __global__ __launch_bounds__(64 * W, MODE == kModeEX ? FWAV_TOPK_EXWPE : (CENT ?
 #pragma unroll
   for (int s = 0; s < QS; ++s) lid[s] = wave * QS + s;
   half8 bc{};          // CENT: the lane's centroid (fp16, MFMA B operand) ...
-  float cslack = 0.0f;  // ... and its slack
+  CentBound cb{};     // ... and its filter threshold's constants
   auto setup_centroids = [&]() {
     const int sj = col % QS, mcol0 = QS * (col / QS);
     int ls = lid[0];
@@ -1680,7 +1687,7 @@ __global__ __launch_bounds__(64 * W, MODE == kModeEX ? FWAV_TOPK_EXWPE : (CENT ?
     centroid_setup<QS>(emb16, [&](int k) -> int64_t {
       const int64_t qi = slot_query(block, qslot0 + ls * 32 + mcol0 + k, plan.nb, QB);
       return qi < n_active ? (int64_t)active[qi] + q_offset : (int64_t)-1;
-    }, bc, cslack);
+    }, bc, cb);
   };
   if constexpr (CENT) setup_centroids();
   const int nchunks = (int)cdiv(nd, kChunk);  // < 2^31 / 256: chunk arithmetic stays 32-bit (scalar)
@@ -1733,6 +1740,10 @@ __global__ __launch_bounds__(64 * W, MODE == kModeEX ? FWAV_TOPK_EXWPE : (CENT ?
   // issued.  (Read after that issue, as rounds 4–5 did, the compiler's wait for the loaded value, vmcnt(0), also
   // waited for the whole next group's DMA: every group's level 1 started only once the group after it had landed.)
   uint32_t shv[QS];
+  // CENT: the lane's filter threshold, recomputed only after a group in which some limit of the wave moved (a
+  // compaction or a piece's shared limit; cfg2: 0.57 compactions per query over a pass of 1,291 groups)
+  int thc = 0;
+  bool thc_stale = true;
   for (int g = 0; g < ngroups; ++g) {
     u32x4(*half)[512] = slots + (g % NB) * G;
     const int cg = c0 + g * G;  // first chunk of group g
@@ -1760,8 +1771,11 @@ __global__ __launch_bounds__(64 * W, MODE == kModeEX ? FWAV_TOPK_EXWPE : (CENT ?
       // CENT: the pieces' shared limits every group (a filter threshold that rises sooner skips more level-2 work),
       // retired by the wait above
 #pragma unroll
-      for (int s = 0; s < QS; ++s)
+      for (int s = 0; s < QS; ++s) {
+        const float t0 = thf[s];
         if (upd[s] && shv[s] != 0u) thf[s] = fmaxf(thf[s], key2f(shv[s]));
+        thc_stale |= __ballot(thf[s] != t0) != 0ull;
+      }
     }
     // (the DMA issued after level 1 or level 2 instead measured no better: profiles/r04/ab_prefix_dma_barrier.log)
     if (g + 1 < ngroups) issue_group(g + 1);
@@ -1771,10 +1785,13 @@ __global__ __launch_bounds__(64 * W, MODE == kModeEX ? FWAV_TOPK_EXWPE : (CENT ?
     for (int s = 0; s < QS; ++s) thi[s] = int_threshold(HL ? thf[s] - kStreamMargin : thf[s]);
     const _Float16* lda0 = reinterpret_cast<const _Float16*>(half[0]) + ((h * kChunk) + col) * 8;
     if constexpr (CENT) {
-      float tv[QS];
+      if (thc_stale) {
+        float tv[QS];
 #pragma unroll
-      for (int s = 0; s < QS; ++s) tv[s] = HL ? thf[s] - kStreamMargin : thf[s];
-      const int thc = centroid_threshold<QS>(tv, cslack);
+        for (int s = 0; s < QS; ++s) tv[s] = HL ? thf[s] - kStreamMargin : thf[s];
+        thc = centroid_threshold<QS>(tv, cb, !(ABL && (dbg & 2048)));
+        thc_stale = false;
+      }
       uint64_t pend[QS];
       const unsigned long long t_l1 = STATS ? __builtin_amdgcn_s_memrealtime() : 0;
       if (c_end - cg == G) {
@@ -1830,10 +1847,12 @@ __global__ __launch_bounds__(64 * W, MODE == kModeEX ? FWAV_TOPK_EXWPE : (CENT ?
               if (__ballot(fold16((int)0x80000000, acc[u]) > thi[s]) != 0ull) pass |= (TMask)1 << t[u];
             } else {
               const int64_t dt = (int64_t)(cg + (t[u] >> 3)) * kChunk + (t[u] & 7) * 32;
+              const float t0 = thf[s];
               thf[s] = append_tile<C, STATS, Topk16SmemT<NG, STATS, !CENT, W>, MODE>(acc[u], thf[s], qcnt[s], kept[s],
                                                                                  dt, nd, gkeys, sm, lid[s], K,
                                                                                  upd[s], stats, sp, emb, qv[s],
                                                                                  &kth[s], share);
+              thc_stale |= __ballot(thf[s] != t0) != 0ull;
             }
           }
         }
@@ -1859,10 +1878,12 @@ __global__ __launch_bounds__(64 * W, MODE == kModeEX ? FWAV_TOPK_EXWPE : (CENT ?
               a2 = __builtin_amdgcn_mfma_f32_32x32x16_f16(af, bl[s], a2, 0, 0, 0);
               a2 = __builtin_amdgcn_mfma_f32_32x32x16_f16(afl[u], b[s], a2, 0, 0, 0);
               const int64_t dt = (int64_t)(cg + (t[u] >> 3)) * kChunk + (t[u] & 7) * 32;
+              const float t0 = thf[s];
               thf[s] = append_tile<C, STATS, Topk16SmemT<NG, STATS, !CENT, W>, MODE>(a2, thf[s], qcnt[s], kept[s], dt,
                                                                                  nd, gkeys, sm, lid[s], K,
                                                                                  upd[s], stats, sp, emb, qv[s],
                                                                                  &kth[s], share);
+              thc_stale |= __ballot(thf[s] != t0) != 0ull;
             }
           }
         }
