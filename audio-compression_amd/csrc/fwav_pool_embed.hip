@@ -18,8 +18,11 @@
 //   transient[k] = f64-DCT(f64(x[n] − x[n−1]) · w[n])[k], k < min(8, rs); ‖·‖ as ddot (n < 16: a sequential f64 fma
 //                  chain) then sqrt; / ‖·‖ if > 1e-8; → f32                                  (fractal.py:154-164)
 // with the DCTs scipy's own pocketfft operation sequence in each precision (fwav_dct.h) and w = np.linspace(1, 2, rs)
-// as numpy computes it (i·(1/(rs−1)) + 1, last = 2).  Other range sizes take the f64 matrix DCT (within 1e-6,
-// SURVEY Appendix A rule 2).  fwav_embed_tables packs the matrices and pocketfft's constants for both precisions.
+// as numpy computes it (i·(1/(rs−1)) + 1, last = 2).  Other range sizes take the f64 matrix DCT and are NOT bit-exact:
+// the tonal head is within 2⁻²² of the exactly rounded (f64) embedding, so its distance from the reference's is the
+// reference's own f32 DCT error (a few 1e-6 at rs 19 and 32, growing with a row's DC/AC ratio; measured figures in
+// DESIGN.md §4a); the transient head is f64 on both sides until one final rounding (within 2⁻²³).  The pool is
+// bit-exact at every size.  fwav_embed_tables packs the matrices and pocketfft's constants for both precisions.
 #include "fwav_common.h"
 #include "fwav_dct.h"
 #include "../../include/fwav.h"

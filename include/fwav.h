@@ -66,7 +66,11 @@ int fwav_debug_smooth(const float* energy, int64_t nf, int smooth_window, float*
  * Replaces build_domains_memmap (fractal.py:285-334) and build_domain_embeddings → multi_head_embedding →
  * tile_embedding / transient_embedding (fractal.py:238-280, 166-208, 154-164).
  * pool f32[n_domains·range_size] (bit-exact), emb f32[n_domains·16] (bit-exact for range_size 4, 8, 16: scipy's own
- * pocketfft DCT sequence in f32 and f64 and numpy's BLAS norm orders; |Δ| ≤ 1e-6 for other range sizes),
+ * pocketfft DCT sequence in f32 and f64 and numpy's BLAS norm orders.  Other range sizes take an f64 matrix DCT and
+ * are not bit-exact: tonal columns 0-7 are within 2^-22 of the exactly rounded embedding, so they differ from the
+ * reference's by the reference's own f32 DCT error (a few 1e-6 at range sizes 19 and 32); transient columns
+ * 8-15 are within 2^-23 of the reference's.  Candidates and match tuples computed from such an embedding can
+ * therefore differ from the reference's on a few rows; every other stage is bit-exact at any range size),
  * emb16 (optional) fp16 copies in the search's tiled layout, f16[fwav_emb16_elems(n_domains)]: the high part
  * f16(emb) then the low part f16(emb − f16(emb)), ceil(n_domains/256)·256·16 halfs each.
  * n_domains = (n − tile) / step + 1.  tab = device copy of fwav_embed_tables(range_size) (host call, tab_host holds

@@ -173,6 +173,11 @@ def main():
         "ragged": (synth.noise(0.05, 44100, seed=3)[:2203], 44100, 4, 1000, 1e-4, (16, 2000), True),
         # fewer than 5 voiced-detection frames (30 samples, frame 8): np.convolve swaps its operands
         "tiny": (synth.noise(30 / 8000, 8000, seed=9), 8000, 4, 16, 1e-4, (8,), True),
+        # range sizes other than 4, 8 and 16 (the runtime-sized branch of every compress stage), all ragged:
+        # rs 32 / step 8 (block 256), rs 19 / step 4 (block 263, tile % rs = 3), rs 5 / step 1 (block 260)
+        "t8192": (synth.speech_like(0.5, 44100, seed=2, floor=False), 44100, 4, 8192, 1e-4, (64,), True),
+        "t5000": (synth.speech_like(0.4, 44100, seed=3, floor=False)[:15013], 44100, 4, 5000, 1e-4, (64, 17), True),
+        "t1300": (synth.noise(0.1, 44100, seed=4)[:4001], 44100, 4, 1300, 1e-4, (32,), True),
     }
     only = sys.argv[1:]
     for name, (sig, fr, sw, tile, thr, Ks, wf) in cases.items():

@@ -3,11 +3,11 @@ tests/golden/make_golden.py from /root/reference/fractal.py).  Bars: SURVEY.md A
 import numpy as np
 import pytest
 
-from golden_util import CASES, bit_equal, load
+from golden_util import CASES, GENERIC_CASES, bit_equal, load
 from oracle import fractal_oracle as O
 
 
-@pytest.mark.parametrize("case", CASES)
+@pytest.mark.parametrize("case", CASES + GENERIC_CASES)
 def test_voiced_ranges_pool_bitexact(case):
     g = load(case)
     p = g["p"]
@@ -21,14 +21,14 @@ def test_voiced_ranges_pool_bitexact(case):
     assert bit_equal(O.domain_pool(g["signal"], p["tile"], rs, step), g["pool"])
 
 
-@pytest.mark.parametrize("case", CASES)
+@pytest.mark.parametrize("case", CASES + GENERIC_CASES)
 def test_embedding_bitexact(case):
     """scipy's own DCT with numpy's BLAS norm orders (sdot: f32 products summed in f64)."""
     g = load(case)
     assert bit_equal(O.embed(g["pool"]), g["emb"])
 
 
-@pytest.mark.parametrize("case", CASES)
+@pytest.mark.parametrize("case", CASES + GENERIC_CASES)
 def test_candidates_bitexact(case):
     """The reference's candidate rows exactly — order included: scores in its sgemv order, ties in numpy's order."""
     g = load(case)
@@ -41,7 +41,7 @@ def test_candidates_bitexact(case):
         assert np.array_equal(cand, gold)
 
 
-@pytest.mark.parametrize("case", CASES)
+@pytest.mark.parametrize("case", CASES + GENERIC_CASES)
 def test_end_to_end_bitexact(case):
     """The oracle from the signal alone (voiced → ranges → pool → embeddings → search → affine) reproduces every
     match tuple of the reference."""
@@ -53,7 +53,7 @@ def test_end_to_end_bitexact(case):
             assert bit_equal(r[nm], g[f"m_{nm}_{K}"]), nm
 
 
-@pytest.mark.parametrize("case", CASES)
+@pytest.mark.parametrize("case", CASES + GENERIC_CASES)
 def test_affine_bitexact(case):
     g = load(case)
     for K in g["p"]["Ks"]:
@@ -62,7 +62,42 @@ def test_affine_bitexact(case):
             assert bit_equal(a, g[f"m_{nm}_{K}"]), nm
 
 
-@pytest.mark.parametrize("case", CASES)
+def test_affine_edges_pinned():
+    """tests/golden/affine_edges.npz (the reference's own _flush_gpu_batch on the edge table of tests/affine_edges.py:
+    all-(−1) rows, −1 tails, constant tiles, mirror pairs, palindromes, clipped s, overflow, inf, NaN, tiny values; rs
+    4/8/16/5/19/32/130, K on both sides of 64, s_clip 16 / 0.5 / −16): the shared builder still makes the recorded
+    inputs, and O.affine reproduces every recorded output bit for bit (a NaN matches any NaN) — which makes O.affine
+    the reference of the wider GPU sweep (tests/test_gpu_affine_edges.py)."""
+    import os
+
+    import affine_edges as AE
+    fx = np.load(os.path.join(os.path.dirname(__file__), "golden", "affine_edges.npz"))
+    assert [tuple(s) for s in fx["shapes"].tolist()] == list(AE.FIXTURE_SHAPES)
+    for rs, K in AE.FIXTURE_SHAPES:
+        tag = f"rs{rs}_k{K}"
+        ranges, cand, pool, names = AE.build(rs, K)
+        assert AE.same_bits_or_nan(ranges, fx[f"ranges_{tag}"]) and AE.same_bits_or_nan(pool, fx[f"pool_{tag}"])
+        assert np.array_equal(cand, fx[f"cand_{tag}"])
+        for ci, sc in enumerate(fx["s_clips"].tolist()):
+            with np.errstate(all="ignore"):
+                out = O.affine(ranges, cand, pool, s_clip=sc)
+            for nm, a in zip(("idx", "s", "o", "sym", "err"), out):
+                assert AE.same_bits_or_nan(a, fx[f"{nm}_{tag}_c{ci}"]), (tag, sc, nm)
+        # the edges do what they are there for (s_clip 16)
+        row = {n: i for i, n in enumerate(names)}
+        idx, s, sym, err = (fx[f"{nm}_{tag}_c0"] for nm in ("idx", "s", "sym", "err"))
+        assert idx[row["all -1"]] == 0 and np.isinf(err[row["all -1"]])
+        assert s[row["s clipped high"]] == 16 and s[row["s clipped low, mirrored"]] == -16
+        assert sym[row["s clipped low, mirrored"]] == 1
+        assert sym[row["palindromic tile"]] == 0
+        assert idx[row["NaN tile in the last slot"]] == AE.P_NAN and np.isnan(err[row["NaN tile in the last slot"]])
+        if K >= 2:
+            assert idx[row["NaN tile after a finite one"]] == AE.P_NAN and sym[row["NaN tile after a finite one"]] == 0
+            # a tile and its stored mirror: each orientation's error appears in an unmirrored slot, which comes first
+            assert sym[row["tile, mirror"]] == 0 and sym[row["mirror, tile"]] == 0
+
+
+@pytest.mark.parametrize("case", CASES + GENERIC_CASES)
 def test_decode_bitexact(case):
     g = load(case)
     p = g["p"]
@@ -105,7 +140,7 @@ def test_decode_early_exit_takes_reference_decision(case):
     assert it == (t + 1 if ref[t] < eps else min(12, next((u + 1 for u in range(t + 1, 12) if ref[u] < eps), 12)))
 
 
-@pytest.mark.parametrize("case", [c for c in CASES if c in ("tone", "sweep", "ragged", "tiny")])
+@pytest.mark.parametrize("case", [c for c in CASES if c in ("tone", "sweep", "ragged", "tiny")] + GENERIC_CASES)
 def test_fwav_bytes(case):
     g = load(case)
     p = g["p"]
@@ -124,7 +159,7 @@ def test_pruned_ranges_emit_domain0_inf():
     assert np.all(g[f"m_idx_{K}"][pr] == 0) and np.all(np.isinf(g[f"m_err_{K}"][pr]))
 
 
-@pytest.mark.parametrize("case", CASES)
+@pytest.mark.parametrize("case", CASES + GENERIC_CASES)
 def test_embedding_heads_at_most_unit_norm(case):
     """The fp16 pre-filter's error bound δ (fwav_topk.hip kF16Delta) assumes every embedding head — tonal dims 0-7,
     transient dims 8-15 — has norm ≤ 1 (fractal.py:205-207, 161-163 normalise; zero rows stay zero)."""
