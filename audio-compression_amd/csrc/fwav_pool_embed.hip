@@ -23,8 +23,19 @@
 // reference's own f32 DCT error (a few 1e-6 at rs 19 and 32, growing with a row's DC/AC ratio; measured figures in
 // DESIGN.md §4a); the transient head is f64 on both sides until one final rounding (within 2⁻²³).  The pool is
 // bit-exact at every size.  fwav_embed_tables packs the matrices and pocketfft's constants for both precisions.
+//
+// Exact embedding at further range sizes (fwav_pool_embed_exact → k_embed_exact, one thread per domain as above): the
+// same two heads with pocketfft's general plan for a runtime n (fwav_dct_plan.h: rfftp's factor order and the passes
+// radb4, radb2, radb3, radb5 and the generic radbg), bit-exact with the reference at every n from 4 to 49 and at 50,
+// 54, 56, 60, 63 and 64 — the lengths at which pocketfft runs that plan and not Bluestein's.  The host builds the plan
+// (dct_plan_build, a kernel argument) and the constants (dct_plan_constants → fwav_embed_tables_exact); a thread's two
+// work buffers are columns of an LDS array, the f32 head then the f64 head in the same storage.  An unsupported range
+// size is an error, never the matrix path; 4, 8 and 16 route to k_embed's fixed plans.  The default entry point stays
+// fwav_pool_embed: tests/test_gpu_generic_rs.py holds it within 2⁻²² of the f64 embedding, which the reference's own
+// f32 DCT is not.
 #include "fwav_common.h"
 #include "fwav_dct.h"
+#include "fwav_dct_plan.h"
 #include "../../include/fwav.h"
 
 #include <utility>
@@ -287,6 +298,229 @@ void dct_constants(int n, bool dbl, double* out) {
   out[2 * n + 10] = r(1.414213562373095048801688724209698L);
 }
 
+
+// ---------------------------------------------------------------------------------------------------------------
+// Exact embedding at any supported range size: pocketfft's general plan (fwav_dct_plan.h) for a runtime n.
+
+// pocketfft takes rfftp (never Bluestein) for n < 50 and wherever (largest prime factor)² ≤ n; up to 64 that is every
+// n but 51, 52, 53, 55, 57, 58, 59, 61 and 62.
+bool dct_plan_supported(int n) {
+  if (n < 4 || n > kPlanMaxN) return false;
+  if (n < 50) return true;
+  int m = n, lpf = 1;
+  for (int d = 2; d * d <= m; ++d)
+    while (m % d == 0) {
+      lpf = d;
+      m /= d;
+    }
+  if (m > 1) lpf = m;
+  return lpf * lpf <= n;
+}
+
+// The plan of length n as a kernel argument (uniform: it lives in scalar registers): rfftp::factorize's factor order
+// and comp_twiddle's offsets into a precision block's twiddle memory; pb = doubles per precision block.
+struct DctPlan {
+  int n, nf, pb;
+  int ip[kPlanMaxFact], tw[kPlanMaxFact], tws[kPlanMaxFact];
+};
+
+bool dct_plan_build(int n, DctPlan& p) {
+  if (!dct_plan_supported(n)) return false;
+  p.n = n;
+  p.nf = 0;
+  for (int k = 0; k < kPlanMaxFact; ++k) p.ip[k] = p.tw[k] = p.tws[k] = 0;
+  int len = n;
+  auto add = [&](int f) {
+    if (p.nf < kPlanMaxFact) p.ip[p.nf] = f;
+    ++p.nf;
+  };
+  while (len % 4 == 0) {
+    add(4);
+    len >>= 2;
+  }
+  if (len % 2 == 0) {
+    len >>= 1;
+    add(2);
+    if (p.nf <= kPlanMaxFact) std::swap(p.ip[0], p.ip[p.nf - 1]);
+  }
+  for (int d = 3; d * d <= len; d += 2)
+    while (len % d == 0) {
+      add(d);
+      len /= d;
+    }
+  if (len > 1) add(len);
+  if (p.nf > kPlanMaxFact) return false;
+  int ptr = 0;
+  for (int k = 0, l1 = 1; k < p.nf; ++k) {
+    const int ip = p.ip[k], ido = n / (l1 * ip);
+    p.tw[k] = ptr;
+    if (k < p.nf - 1) ptr += (ip - 1) * (ido - 1);  // the last factor needs no twiddles
+    if (ip > 5) {
+      p.tws[k] = ptr;
+      ptr += 2 * ip;
+    }
+    l1 *= ip;
+  }
+  p.pb = kPlanConst + n + ptr;
+  return p.pb <= plan_block_max(n);
+}
+
+// One precision block of the plan's constants (fwav_dct_plan.h's layout), T = double if dbl else float, exactly as
+// pocketfft computes them: comp_twiddle's entries of sincos_2pibyn(n), T_dcst23's of sincos_2pibyn(4n), long-double
+// literals rounded once to T.
+void dct_plan_constants(const DctPlan& p, bool dbl, double* out) {
+  auto r = [&](long double v) { return dbl ? (double)v : (double)(float)v; };
+  const int n = p.n;
+  out[0] = r(1.0L / std::sqrt((long double)(2 * n)));
+  out[1] = r(1.414213562373095048801688724209698L);
+  out[2] = r(0.8660254037844386467637231707529362L);
+  out[3] = r(0.3090169943749474241022934171828191L);
+  out[4] = r(0.9510565162951535721164393333793821L);
+  out[5] = r(-0.8090169943749474241022934171828191L);
+  out[6] = r(0.5877852522924731291687059546390728L);
+  out[7] = 0.0;
+  const SinCos2PiByN s4(4 * (size_t)n), s1((size_t)n);
+  for (int i = 0; i < n; ++i) out[kPlanConst + i] = r(s4[i + 1].first);
+  double* mem = out + kPlanConst + n;
+  for (int i = kPlanConst + n; i < p.pb; ++i) out[i] = 0.0;  // an even ido leaves one slot per twiddle row unused
+  for (int k = 0, l1 = 1; k < p.nf; ++k) {
+    const int ip = p.ip[k], ido = n / (l1 * ip);
+    if (k < p.nf - 1) {
+      double* tw = mem + p.tw[k];
+      for (int j = 1; j < ip; ++j)
+        for (int i = 1; i <= (ido - 1) / 2; ++i) {
+          tw[(j - 1) * (ido - 1) + 2 * i - 2] = r(s1[(size_t)j * l1 * i].first);
+          tw[(j - 1) * (ido - 1) + 2 * i - 1] = r(s1[(size_t)j * l1 * i].second);
+        }
+    }
+    if (ip > 5) {
+      double* tws = mem + p.tws[k];
+      tws[0] = 1.0;
+      tws[1] = 0.0;
+      for (int i = 2, ic = 2 * ip - 2; i <= ic; i += 2, ic -= 2) {
+        const auto t = s1[(size_t)(i / 2) * (n / ip)];
+        tws[i] = r(t.first);
+        tws[i + 1] = r(t.second);
+        tws[ic] = r(t.first);
+        tws[ic + 1] = r(-t.second);
+      }
+    }
+    l1 *= ip;
+  }
+}
+
+template <class T>
+FWAV_HD PlanK<T> plan_view(const DctPlan& p, const T* block) {
+  PlanK<T> v;
+  v.n = p.n;
+  v.nf = p.nf;
+  for (int k = 0; k < kPlanMaxFact; ++k) {
+    v.ip[k] = p.ip[k];
+    v.tw[k] = p.tw[k];
+    v.tws[k] = p.tws[k];
+  }
+  v.k = block;
+  return v;
+}
+
+constexpr int kExactThreads = 64;
+
+// One thread per domain row, as k_embed's exact branch, for a runtime n ≤ NMAX.  The two DCT work buffers of a thread
+// are columns of s_buf (element i of lane t at i·64 + t: conflict-free, nothing indexed at run time lives in
+// registers or scratch); the f32 head and then the f64 head run in the same storage.  The plan arrives as a kernel
+// argument, both precisions' constants and w are staged in LDS (uniform reads broadcast).  NMAX = 64 takes 68,640 B
+// of LDS: two workgroups per CU.
+template <int NMAX>
+__global__ __launch_bounds__(kExactThreads) void k_embed_exact(const float* __restrict__ src, int64_t nd, int64_t a,
+                                                               int64_t b, const double* __restrict__ tab,
+                                                               const DctPlan plan, float* __restrict__ pool_out,
+                                                               float* __restrict__ emb, _Float16* __restrict__ emb16) {
+  __shared__ double s_buf[2 * NMAX * kExactThreads];
+  __shared__ double s_kd[plan_block_max(NMAX)];
+  __shared__ double s_w[NMAX];
+  __shared__ float s_kf[plan_block_max(NMAX)];
+  const int tid = threadIdx.x;
+  const int n = plan.n;
+  for (int i = tid; i < plan.pb; i += kExactThreads) {
+    s_kf[i] = (float)tab[kPlanHead + n + i];
+    s_kd[i] = tab[kPlanHead + n + plan.pb + i];
+  }
+  for (int i = tid; i < n; i += kExactThreads) s_w[i] = tab[kPlanHead + i];
+  __syncthreads();
+  const int64_t d = (int64_t)blockIdx.x * kExactThreads + tid;
+  if (d >= nd) return;
+  const float* xs = src + d * a;
+  const int take = n - 1 < 8 ? n - 1 : 8;
+  const int tk = n < 8 ? n : 8;
+  float e[8], tf[8];
+  {
+    // tonal head: f32 pocketfft DCT, · w in f64 → f32, sdot-order norm, f32 divide
+    float* fb = reinterpret_cast<float*>(s_buf);
+    const Col<float, kExactThreads> c{fb + tid}, ch{fb + NMAX * kExactThreads + tid};
+    for (int i = 0; i < n; ++i) {
+      const float v = xs[i * b];
+      if (pool_out) pool_out[d * n + i] = v;
+      c[i] = v;
+    }
+    dct2_ortho_plan<float>(c, ch, plan_view<float>(plan, s_kf));
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int i = j + 1 < n ? j + 1 : 0;
+      e[j] = j < take ? (float)((double)c[i] * s_w[i]) : 0.0f;
+    }
+    double acc = 0.0;  // sdot: f32 products, f64 sum in index order, f32 result
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc = acc + (double)(e[j] * e[j]);
+    const float nrm = sqrtf((float)acc);
+    if (nrm > 1e-8f) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) e[j] = e[j] / nrm;
+    }
+  }
+  __atomic_signal_fence(__ATOMIC_SEQ_CST);  // the f64 head reuses the f32 head's storage: keep the compiler's order
+  {
+    // transient head: f64 pocketfft DCT of the weighted first difference, ddot fma-chain norm, divide, → f32
+    const Col<double, kExactThreads> c{s_buf + tid}, ch{s_buf + NMAX * kExactThreads + tid};
+    float xp = xs[0];
+    for (int i = 0; i < n; ++i) {
+      const float xi = xs[i * b];
+      c[i] = (double)(i == 0 ? xi - xi : xi - xp) * s_w[i];
+      xp = xi;
+    }
+    dct2_ortho_plan<double>(c, ch, plan_view<double>(plan, s_kd));
+    double s2 = 0.0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      if (j < tk) s2 = __builtin_fma(c[j], c[j], s2);
+    const double nrmd = sqrt(s2);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      double v = j < tk ? c[j] : 0.0;
+      if (nrmd > 1e-8) v = v / nrmd;
+      tf[j] = (float)v;
+    }
+  }
+  // concatenation [tonal 8 | transient tk] then zero pad to 16, as k_embed
+  float out[16];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) out[j] = e[j];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) out[8 + j] = j < tk ? tf[j] : 0.0f;
+  float4* o4 = reinterpret_cast<float4*>(emb + d * 16);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) o4[j] = make_float4(out[4 * j], out[4 * j + 1], out[4 * j + 2], out[4 * j + 3]);
+  if (emb16 != nullptr) store_emb16(emb16, nd, d, out);
+}
+
+template <int NMAX>
+static void launch_embed_exact(const float* src, int64_t nd, int64_t a, int64_t b, const double* tab,
+                               const DctPlan& plan, float* pool_out, float* emb, _Float16* emb16, hipStream_t st) {
+  k_embed_exact<NMAX><<<cdiv(nd, kExactThreads), kExactThreads, 0, st>>>(src, nd, a, b, tab, plan, pool_out, emb,
+                                                                         emb16);
+}
+
+static bool exact_routes_fixed(int rs) { return rs == 4 || rs == 8 || rs == 16; }
+
 }  // namespace fwav
 
 using namespace fwav;
@@ -347,6 +581,61 @@ int fwav_debug_dct2(int n, int dbl, const double* x, double* out) {
   } else {
     if (n == 4) run(0.0f, I4{}); else if (n == 8) run(0.0f, I8{}); else run(0.0f, I16{});
   }
+  return FWAV_OK;
+}
+
+// ---- exact embedding (scipy's pocketfft DCTs at any supported range size)
+int fwav_embed_exact_supported(int rs) { return exact_routes_fixed(rs) || dct_plan_supported(rs) ? 1 : 0; }
+
+// Host-side table of fwav_pool_embed_exact: for rs = 4, 8, 16 fwav_embed_tables' own (those sizes run k_embed's fixed
+// plans); otherwise the plan, w = np.linspace(1, 2, rs) and both precisions' constants (fwav_dct_plan.h's layout).
+size_t fwav_embed_tables_exact_size(int rs) {
+  if (exact_routes_fixed(rs)) return fwav_embed_tables_size(rs);
+  DctPlan p;
+  if (!dct_plan_build(rs, p)) return 0;
+  return (size_t)kPlanHead + rs + 2 * (size_t)p.pb;
+}
+
+int fwav_embed_tables_exact(int rs, double* tab) {
+  FWAV_CHECK_ARG(tab, FWAV_ERR_ARG, "fwav_embed_tables_exact: null table");
+  if (exact_routes_fixed(rs)) return fwav_embed_tables(rs, tab);
+  DctPlan p;
+  FWAV_CHECK_ARG(dct_plan_build(rs, p), FWAV_ERR_ARG,
+                 "fwav_embed_tables_exact: range size %d has no exact pocketfft plan (4 ... 49, 50, 54, 56, 60, 63, 64)",
+                 rs);
+  for (int i = 0; i < kPlanHead; ++i) tab[i] = 0.0;
+  tab[0] = rs;
+  tab[1] = p.nf;
+  for (int k = 0; k < kPlanMaxFact; ++k) {
+    tab[2 + 3 * k] = p.ip[k];
+    tab[3 + 3 * k] = p.tw[k];
+    tab[4 + 3 * k] = p.tws[k];
+  }
+  tab[14] = p.pb;
+  const double step = 1.0 / (double)(rs - 1);
+  for (int i = 0; i < rs; ++i) tab[kPlanHead + i] = i == rs - 1 ? 2.0 : (double)i * step + 1.0;
+  dct_plan_constants(p, false, tab + kPlanHead + rs);
+  dct_plan_constants(p, true, tab + kPlanHead + rs + p.pb);
+  return FWAV_OK;
+}
+
+// Test hook (host): scipy.fftpack.dct(x, norm='ortho') of n doubles (dbl = 1) or floats (dbl = 0, passed and returned
+// as doubles) through fwav_dct_plan.h — the code k_embed_exact runs, instantiated on the host with stride-1 buffers.
+int fwav_debug_dct2_plan(int n, int dbl, const double* x, double* out) {
+  FWAV_CHECK_ARG(x && out, FWAV_ERR_ARG, "fwav_debug_dct2_plan: null array");
+  DctPlan p;
+  FWAV_CHECK_ARG(dct_plan_build(n, p), FWAV_ERR_ARG, "fwav_debug_dct2_plan: n = %d has no exact pocketfft plan", n);
+  double kd[plan_block_max(kPlanMaxN)];
+  dct_plan_constants(p, dbl != 0, kd);
+  auto run = [&](auto tag) {
+    using T = decltype(tag);
+    T k[plan_block_max(kPlanMaxN)], c[kPlanMaxN], ch[kPlanMaxN];
+    for (int i = 0; i < p.pb; ++i) k[i] = (T)kd[i];
+    for (int i = 0; i < n; ++i) c[i] = (T)x[i];
+    dct2_ortho_plan<T>(Col<T, 1>{c}, Col<T, 1>{ch}, plan_view<T>(p, k));
+    for (int i = 0; i < n; ++i) out[i] = (double)c[i];
+  };
+  if (dbl) run(0.0); else run(0.0f);
   return FWAV_OK;
 }
 
@@ -424,6 +713,59 @@ int fwav_pool_embed(const float* sig, int64_t n, int tile, int rs, int step, con
     default: launch_embed<0>(src, nd, rs, a, b, tab, pool_out, emb, e16, st); break;
   }
   FWAV_LAUNCH_CHECK("fwav_pool_embed");
+  return FWAV_OK;
+}
+
+// fwav_pool_embed with the exact embedding kernel: the same pool stage on both source layouts, then k_embed_exact.
+// tab: device copy of fwav_embed_tables_exact(rs).  rs = 4, 8, 16: fwav_pool_embed itself (already exact).
+int fwav_pool_embed_exact(const float* sig, int64_t n, int tile, int rs, int step, const double* tab, float* pool,
+                          float* emb, void* emb16, void* workspace, size_t ws_bytes, void* stream) {
+  if (exact_routes_fixed(rs))
+    return fwav_pool_embed(sig, n, tile, rs, step, tab, pool, emb, emb16, workspace, ws_bytes, stream);
+  FWAV_CHECK_ARG(sig && pool && emb && tab && tile > 0 && rs > 0 && step > 0, FWAV_ERR_ARG,
+                 "fwav_pool_embed_exact: bad args");
+  DctPlan plan;
+  FWAV_CHECK_ARG(dct_plan_build(rs, plan), FWAV_ERR_ARG,
+                 "fwav_pool_embed_exact: range size %d has no exact pocketfft plan (fwav_embed_exact_supported)", rs);
+  FWAV_CHECK_ARG(n >= tile, FWAV_ERR_SHAPE, "fwav_pool_embed_exact: n < tile");
+  const int bl = tile / rs;
+  FWAV_CHECK_ARG(bl >= 1 && bl <= kMaxPairwise, FWAV_ERR_SHAPE, "fwav_pool_embed_exact: block length out of range");
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t nd = (n - tile) / step + 1;
+  const float* src;
+  int64_t a, b;
+  float* pool_out;
+  if (bl % step == 0) {
+    FWAV_CHECK_ARG(ws_bytes >= fwav_pool_workspace_size(n, tile, rs, step) && workspace, FWAV_ERR_WORKSPACE,
+                   "fwav_pool_embed_exact: workspace too small");
+    const int64_t m = bl / step;
+    const int64_t ns = (nd - 1) + (int64_t)(rs - 1) * m + 1;
+    float* S = (float*)workspace;
+    const int64_t g = cdiv(ns, kPoolThreads);
+    if (bl == 256) k_block_means<256><<<g, kPoolThreads, 0, st>>>(sig, ns, step, bl, S);
+    else if (bl == 128) k_block_means<128><<<g, kPoolThreads, 0, st>>>(sig, ns, step, bl, S);
+    else k_block_means<0><<<g, kPoolThreads, 0, st>>>(sig, ns, step, bl, S);
+    src = S; a = 1; b = m; pool_out = pool;
+  } else {
+    k_domain_pool<<<cdiv(nd * rs, kPoolThreads), kPoolThreads, 0, st>>>(sig, nd, rs, step, bl, pool);
+    src = pool; a = rs; b = 1; pool_out = nullptr;
+  }
+  _Float16* e16 = (_Float16*)emb16;
+  if (e16 != nullptr && (nd & 255) != 0) {
+    // zero the padded tail of the last chunk (both halves of both tables)
+    const int64_t c = nd >> 8, j0 = nd & 255;
+    const int64_t n16 = ((nd + 255) >> 8) * 256 * 16;
+    for (int tb = 0; tb < 2; ++tb)
+      for (int hh = 0; hh < 2; ++hh)
+        (void)hipMemsetAsync(e16 + tb * n16 + ((c * 2 + hh) * 256 + j0) * 8, 0,
+                             (size_t)(256 - j0) * 8 * sizeof(_Float16), st);
+  }
+  if (rs <= 16) launch_embed_exact<16>(src, nd, a, b, tab, plan, pool_out, emb, e16, st);
+  else if (rs <= 24) launch_embed_exact<24>(src, nd, a, b, tab, plan, pool_out, emb, e16, st);
+  else if (rs <= 32) launch_embed_exact<32>(src, nd, a, b, tab, plan, pool_out, emb, e16, st);
+  else if (rs <= 48) launch_embed_exact<48>(src, nd, a, b, tab, plan, pool_out, emb, e16, st);
+  else launch_embed_exact<64>(src, nd, a, b, tab, plan, pool_out, emb, e16, st);
+  FWAV_LAUNCH_CHECK("fwav_pool_embed_exact");
   return FWAV_OK;
 }
 

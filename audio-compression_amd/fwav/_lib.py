@@ -40,6 +40,11 @@ SIGNATURES = {
     "fwav_debug_dct2": (I32, [I32, I32, P, P]),
     "fwav_pool_workspace_size": (SZ, [I64, I32, I32, I32]),
     "fwav_pool_embed": (I32, [P, I64, I32, I32, I32, P, P, P, P, P, SZ, P]),
+    "fwav_embed_exact_supported": (I32, [I32]),
+    "fwav_embed_tables_exact_size": (SZ, [I32]),
+    "fwav_embed_tables_exact": (I32, [I32, P]),
+    "fwav_pool_embed_exact": (I32, [P, I64, I32, I32, I32, P, P, P, P, P, SZ, P]),
+    "fwav_debug_dct2_plan": (I32, [I32, I32, P, P]),
     "fwav_topk_max_k": (I32, []),
     "fwav_sim_topk_workspace_size": (SZ, [I64, I64, I32]),
     "fwav_sim_topk": (I32, [P, P, I64, P, P, I64, I64, I32, I32, P, P, P, SZ, P]),

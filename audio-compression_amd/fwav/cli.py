@@ -1,9 +1,12 @@
 """Command line, same sub-commands / flags / output naming as the reference (fractal.py:1550-1669).
 
   python fractal.py compress IN OUT [--tile 1024] [--energy-thresh 1e-4] [--gpu] [--batch] [--out DIR] [--workers 4]
+                            [--embedding {matrix,pocketfft}]
   python fractal.py decompress IN [--out PATH] [--iter 8] [--eps 1e-3] [--gpu] [--batch] [--workers 4]
 
-Non-batch OUTPUT / --out are used as directories (quirk Q8, fractal.py:1509, 1538).  Batch mode skips
+--embedding is this port's one extra flag: "pocketfft" embeds with scipy's own DCT sequence at every supported range
+size (tiles of 4352 samples and more then give the reference's file too); the default "matrix" is bit-exact at range
+sizes 4, 8 and 16.  Non-batch OUTPUT / --out are used as directories (quirk Q8, fractal.py:1509, 1538).  Batch mode skips
 files whose output exists and writes compression_metrics.json / decompression_metrics.json.  The reference's
 file-level Pool (fractal.py:1596-1600, 1640-1644) becomes one worker process per GPU (at most --workers of them):
 each worker is pinned to its own device at start-up and takes files from the shared queue, so a node's GPUs work
@@ -74,6 +77,9 @@ def main(argv=None):
     pc.add_argument("--gpu", action="store_true")
     pc.add_argument("--batch", action="store_true", help="treat input as directory and compress all WAV inside")
     pc.add_argument("--workers", type=int, default=4, help="parallel file-level workers for batch")
+    pc.add_argument("--embedding", choices=("matrix", "pocketfft"), default="matrix",
+                    help="domain embedding: the matrix DCT (bit-exact at range sizes 4, 8, 16) or scipy's pocketfft "
+                         "sequence (bit-exact at every supported range size; an unsupported one is an error)")
     pd = sub.add_parser("decompress")
     pd.add_argument("input", help="input file or directory")
     pd.add_argument("--out", default=None, help="output file or directory")
@@ -88,7 +94,7 @@ def main(argv=None):
         if not args.batch:
             if args.output is None:
                 parser.error("compress requires OUTPUT unless --batch is used")
-            return _compress_job((args.input, args.output, args.tile, args.energy_thresh, args.gpu))
+            return _compress_job((args.input, args.output, args.tile, args.energy_thresh, args.gpu, args.embedding))
         if args.output is not None:
             parser.error("Do not provide positional OUTPUT when using --batch; use --out instead")
         out_dir = args.out or args.input
@@ -99,7 +105,8 @@ def main(argv=None):
             logger.info("No files to compress — all already exist.")
             return None
         results = _run_pool(_compress_job, [(f, os.path.join(out_dir, os.path.basename(f) + ".fwav"), args.tile,
-                                             args.energy_thresh, args.gpu) for f in todo], args.workers)
+                                             args.energy_thresh, args.gpu, args.embedding) for f in todo],
+                            args.workers)
         metrics_file = os.path.join(out_dir, "compression_metrics.json")
         os.makedirs(os.path.dirname(metrics_file) or ".", exist_ok=True)
         with open(metrics_file, "w") as mf:

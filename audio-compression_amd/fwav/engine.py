@@ -56,11 +56,30 @@ def _p(t: Optional[torch.Tensor]) -> Optional[int]:
 _TABLES: dict = {}
 
 
-def embed_tables(rs: int, device: torch.device) -> torch.Tensor:
-    key = (rs, str(device))
+#: embedding → (tables size call, tables call, pool + embedding call).  "matrix": bit-exact at range sizes 4, 8 and
+#: 16, an f64 matrix DCT elsewhere; "pocketfft": scipy's own DCT sequence, bit-exact at every supported range size
+EMBEDDINGS = {"matrix": ("fwav_embed_tables_size", "fwav_embed_tables", "fwav_pool_embed"),
+              "pocketfft": ("fwav_embed_tables_exact_size", "fwav_embed_tables_exact", "fwav_pool_embed_exact")}
+
+
+def check_embedding(embedding: str, rs: int) -> str:
+    """``embedding`` validated for range size ``rs``: ValueError for an unknown mode, and for "pocketfft" at a range
+    size with no exact plan (there is no silent fall-back to the matrix DCT)."""
+    if embedding not in EMBEDDINGS:
+        raise ValueError(f"embedding must be 'matrix' or 'pocketfft', not {embedding!r}")
+    if embedding == "pocketfft" and not size_call("fwav_embed_exact_supported", int(rs)):
+        raise ValueError(f"embedding='pocketfft' has no exact plan for range size {rs} (supported: 4 to 49 and 50, 54, "
+                         "56, 60, 63, 64); use embedding='matrix'")
+    return embedding
+
+
+def embed_tables(rs: int, device: torch.device, embedding: str = "matrix") -> torch.Tensor:
+    check_embedding(embedding, rs)
+    key = (rs, str(device), embedding)
     if key not in _TABLES:
-        host = np.zeros(size_call("fwav_embed_tables_size", rs), np.float64)
-        call("fwav_embed_tables", rs, host.ctypes.data)
+        size_fn, fill_fn, _ = EMBEDDINGS[embedding]
+        host = np.zeros(size_call(size_fn, rs), np.float64)
+        call(fill_fn, rs, host.ctypes.data)
         _TABLES[key] = torch.from_numpy(host).to(device)
     return _TABLES[key]
 
@@ -187,7 +206,7 @@ def _compress_device(sig: torch.Tensor, tile_size: int, top_k: int, energy_thres
                      keep_intermediates: bool = False, events: Optional[dict] = None,
                      search: str = "f16", on_pool=None, blas_threads: Optional[int] = None,
                      tie_order: str = "numpy", defer_ties: bool = False,
-                     sub_blocks: Optional[int] = None) -> DeviceCompressed:
+                     sub_blocks: Optional[int] = None, embedding: str = "matrix") -> DeviceCompressed:
     """Run the compress hot path on ``sig`` (1-D float32 tensor on a HIP device).
 
     ``shard=(lo, hi)`` restricts candidate search and the affine solve to ranges ``[lo, hi)`` (the
@@ -209,6 +228,10 @@ def _compress_device(sig: torch.Tensor, tile_size: int, top_k: int, energy_thres
     stream of calls overlaps one call's host ranking with the next call's search.  Without deferral, a large search
     over a large table runs as ``sub_blocks`` launches over consecutive slices of the active list (default
     :func:`_tie_sub_blocks`), and each slice's tied rows are ranked on the host while the next slice searches.
+    ``embedding="matrix"`` (default) embeds with the reference's DCT sequence at range sizes 4, 8 and 16 and an f64
+    matrix DCT elsewhere; ``"pocketfft"`` runs scipy's own pocketfft sequence at every supported range size (4 to 49
+    and 50, 54, 56, 60, 63, 64: tiles up to 12,799 and a few above), so the embedding, and with it every candidate set
+    and match, is the reference's bit for bit there too; ValueError at any other range size.
     """
     if sig.dim() != 1 or sig.dtype != torch.float32 or not sig.is_cuda:
         raise ValueError("compress_device expects a 1-D float32 device tensor")
@@ -228,6 +251,7 @@ def _compress_device(sig: torch.Tensor, tile_size: int, top_k: int, energy_thres
     lo32 = F32(energy_thresh * 0.5)
     if k > size_call("fwav_topk_max_k"):
         raise ValueError(f"top_k={k} > {size_call('fwav_topk_max_k')} is not supported by the HIP search")
+    check_embedding(embedding, rs)
     if tie_order not in TIE_MODES:
         raise ValueError("tie_order must be 'numpy' (the reference's order of exactly tied scores wherever it decides a"
                          " match), 'numpy_sets' (and wherever it decides a candidate set), 'numpy_rows' (and wherever it"
@@ -247,7 +271,7 @@ def _compress_device(sig: torch.Tensor, tile_size: int, top_k: int, energy_thres
         if res.is_silent() or n < tile_size:
             return _empty(n, rs, tile_size, step, energy_thresh, k)
         raise ValueError("mmap length is greater than file size")  # quirk Q9 (fractal.py:1190-1195)
-    tab = embed_tables(rs, dev)
+    tab = embed_tables(rs, dev, embedding)
     pool = torch.empty(nd * rs, dtype=torch.float32, device=dev)
     emb = torch.empty(nd * 16, dtype=torch.float32, device=dev)
     if search not in ("f16", "f32"):
@@ -256,8 +280,8 @@ def _compress_device(sig: torch.Tensor, tile_size: int, top_k: int, energy_thres
     ws_p = size_call("fwav_pool_workspace_size", n, tile_size, rs, step)
     wsp = torch.empty(max(ws_p, 16), dtype=torch.uint8, device=dev)
     _mark(events, "pool_embed")
-    call("fwav_pool_embed", sig.data_ptr(), n, tile_size, rs, step, tab.data_ptr(), pool.data_ptr(), emb.data_ptr(),
-         _p(emb16), wsp.data_ptr(), ws_p, st)
+    call(EMBEDDINGS[embedding][2], sig.data_ptr(), n, tile_size, rs, step, tab.data_ptr(), pool.data_ptr(),
+         emb.data_ptr(), _p(emb16), wsp.data_ptr(), ws_p, st)
     _mark(events, "pool_embed")
     if on_pool is not None:
         on_pool(pool)

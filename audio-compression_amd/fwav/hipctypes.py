@@ -122,20 +122,38 @@ def affine_batch(ranges: np.ndarray, cand: np.ndarray, pool: np.ndarray, s_clip:
             outs[3].to_array(np.uint8, B), outs[4].to_array(np.float32, B))
 
 
-def pool_embed(signal: np.ndarray, tile: int, rs: int, step: int):
+#: embedding → (tables size call, tables call, pool + embedding call), as fwav.engine.EMBEDDINGS
+EMBEDDINGS = {"matrix": ("fwav_embed_tables_size", "fwav_embed_tables", "fwav_pool_embed"),
+              "pocketfft": ("fwav_embed_tables_exact_size", "fwav_embed_tables_exact", "fwav_pool_embed_exact")}
+
+
+def _embed_tables(rs: int, embedding: str) -> np.ndarray:
+    """The host table of the embedding mode; ValueError for an unknown mode and for "pocketfft" at a range size with
+    no exact plan (no fall-back to the matrix DCT)."""
+    if embedding not in EMBEDDINGS:
+        raise ValueError(f"embedding must be 'matrix' or 'pocketfft', not {embedding!r}")
+    if embedding == "pocketfft" and not size_call("fwav_embed_exact_supported", int(rs)):
+        raise ValueError(f"embedding='pocketfft' has no exact plan for range size {rs} (supported: 4 to 49 and 50, 54, "
+                         "56, 60, 63, 64); use embedding='matrix'")
+    size_fn, fill_fn, _ = EMBEDDINGS[embedding]
+    tab = np.empty(size_call(size_fn, rs), np.float64)
+    call(fill_fn, rs, tab.ctypes.data)
+    return tab
+
+
+def pool_embed(signal: np.ndarray, tile: int, rs: int, step: int, embedding: str = "matrix"):
     """build_domains_memmap + build_domain_embeddings (fractal.py:285-334, 238-280) →
-    (pool f32[nd, rs], emb f32[nd, 16])."""
+    (pool f32[nd, rs], emb f32[nd, 16]).  ``embedding`` as :func:`compress`."""
     sig = np.ascontiguousarray(signal, np.float32)
     n = sig.size
     nd = (n - tile) // step + 1
-    tab = np.empty(size_call("fwav_embed_tables_size", rs), np.float64)
-    call("fwav_embed_tables", rs, tab.ctypes.data)
+    tab = _embed_tables(rs, embedding)
     ds, dt = DeviceBuffer.from_array(sig), DeviceBuffer.from_array(tab)
     dpool, demb = DeviceBuffer(4 * nd * rs), DeviceBuffer(4 * nd * 16)
     wsn = size_call("fwav_pool_workspace_size", n, tile, rs, step)
     dws = DeviceBuffer(wsn)
-    call("fwav_pool_embed", ds.value, n, tile, rs, step, dt.value, dpool.value, demb.value, None, dws.value, wsn,
-         None)
+    call(EMBEDDINGS[embedding][2], ds.value, n, tile, rs, step, dt.value, dpool.value, demb.value, None, dws.value,
+         wsn, None)
     call("fwav_stream_sync", None)
     return dpool.to_array(np.float32, nd * rs).reshape(nd, rs), demb.to_array(np.float32, nd * 16).reshape(nd, 16)
 
@@ -145,7 +163,8 @@ def _i32(buf: DeviceBuffer, count: int) -> np.ndarray:
 
 
 def compress(signal: np.ndarray, tile_size: int, top_k: int, energy_thresh: float = 1e-4, fast_mode: bool = True,
-             s_clip: float = 16.0, tie_order: str = "numpy", threads: int | None = None) -> dict | None:
+             s_clip: float = 16.0, tie_order: str = "numpy", threads: int | None = None,
+             embedding: str = "matrix") -> dict | None:
     """compress_audio's device pipeline (fractal.py:1040-1256) with HIP buffers only, on the null stream:
 
       fwav_voiced_ranges → fwav_weighted_energy (silent test, :1083) → fwav_pool_embed → fwav_prune → fwav_sim_topk
@@ -156,7 +175,8 @@ def compress(signal: np.ndarray, tile_size: int, top_k: int, energy_thresh: floa
     reference's ValueErrors (empty input; more ranges than domains, quirk Q9), else a dict of host arrays: idx, s, o,
     sym, err (the match tuples), pool f32[nd, rs], emb f32[nd, 16], cand i32[nr, K], n_ranges, range_size,
     domain_step, n_domains, n_ties, n_resolved.  ``tie_order`` as fwav.engine.compress_device ("numpy",
-    "numpy_sets", "numpy_rows" or "index")."""
+    "numpy_sets", "numpy_rows" or "index"), ``embedding`` too: "matrix" (fwav_pool_embed) or "pocketfft"
+    (fwav_pool_embed_exact: scipy's DCT sequence at every supported range size, ValueError at the others)."""
     modes = {"numpy": 0, "numpy_sets": 1, "numpy_rows": 2, "index": -1}  # → fwav_tie_check's exact_sets
     if tie_order not in modes:
         raise ValueError("tie_order must be 'numpy', 'numpy_sets', 'numpy_rows' or 'index'")
@@ -166,6 +186,7 @@ def compress(signal: np.ndarray, tile_size: int, top_k: int, energy_thresh: floa
         raise ValueError("a cannot be empty")  # np.convolve on zero frames (fractal.py:895)
     k = int(top_k)
     rs, step = geometry(tile_size)
+    tab = _embed_tables(rs, embedding)
     frame = 2 * rs
     nr = -(-n // rs)
     nd = 0 if n < tile_size else (n - tile_size) // step + 1
@@ -187,14 +208,12 @@ def compress(signal: np.ndarray, tile_size: int, top_k: int, energy_thresh: floa
         raise ValueError("mmap length is greater than file size")  # quirk Q9 (fractal.py:1190-1195)
     if silent:
         return None
-    tab = np.empty(size_call("fwav_embed_tables_size", rs), np.float64)
-    call("fwav_embed_tables", rs, tab.ctypes.data)
     d_tab = DeviceBuffer.from_array(tab)
     d_pool, d_emb = DeviceBuffer(4 * nd * rs), DeviceBuffer(4 * nd * 16)
     d_emb16 = DeviceBuffer(2 * size_call("fwav_emb16_elems", nd))
     wsp = size_call("fwav_pool_workspace_size", n, tile_size, rs, step)
     d_wsp = DeviceBuffer(wsp)
-    call("fwav_pool_embed", d_sig.value, n, tile_size, rs, step, d_tab.value, d_pool.value, d_emb.value,
+    call(EMBEDDINGS[embedding][2], d_sig.value, n, tile_size, rs, step, d_tab.value, d_pool.value, d_emb.value,
          d_emb16.value, d_wsp.value, wsp, None)
     d_cand, d_active, d_nact = DeviceBuffer(4 * nr * k), DeviceBuffer(4 * nr), DeviceBuffer(4)
     d_zc = DeviceBuffer.from_array(zero_query_candidates(nd, k))

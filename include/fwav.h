@@ -70,7 +70,8 @@ int fwav_debug_smooth(const float* energy, int64_t nf, int smooth_window, float*
  * are not bit-exact: tonal columns 0-7 are within 2^-22 of the exactly rounded embedding, so they differ from the
  * reference's by the reference's own f32 DCT error (a few 1e-6 at range sizes 19 and 32); transient columns
  * 8-15 are within 2^-23 of the reference's.  Candidates and match tuples computed from such an embedding can
- * therefore differ from the reference's on a few rows; every other stage is bit-exact at any range size),
+ * therefore differ from the reference's on a few rows; every other stage is bit-exact at any range size, and
+ * fwav_pool_embed_exact below gives the reference's embedding at those range sizes too),
  * emb16 (optional) fp16 copies in the search's tiled layout, f16[fwav_emb16_elems(n_domains)]: the high part
  * f16(emb) then the low part f16(emb − f16(emb)), ceil(n_domains/256)·256·16 halfs each.
  * n_domains = (n − tile) / step + 1.  tab = device copy of fwav_embed_tables(range_size) (host call, tab_host holds
@@ -87,6 +88,24 @@ int fwav_debug_dct2(int n, int dbl, const double* x, double* out);
 size_t fwav_pool_workspace_size(int64_t n, int tile, int range_size, int step);
 int fwav_pool_embed(const float* sig, int64_t n, int tile, int range_size, int step, const double* tab, float* pool,
                     float* emb, void* emb16, void* workspace, size_t ws_bytes, void* stream);
+/* The exact embedding at further range sizes: fwav_pool_embed with emb bit-exact at every range size for which
+ * fwav_embed_exact_supported() returns 1 — 4 … 49 and 50, 54, 56, 60, 63, 64, the lengths up to 64 at which scipy's
+ * pocketfft runs its factorised real-FFT plan (n < 50 or (largest prime factor)² ≤ n), whose operation sequence the
+ * kernel reproduces in f32 (tonal head) and f64 (transient head).  Same arguments and outputs as fwav_pool_embed,
+ * except tab = device copy of fwav_embed_tables_exact(range_size) (fwav_embed_tables_exact_size doubles; 0 for an
+ * unsupported size).  An unsupported range size is FWAV_ERR_ARG from both calls: there is no fall-back to the matrix
+ * DCT.  At range sizes 4, 8 and 16 both calls are fwav_embed_tables / fwav_pool_embed themselves.  Measured cost:
+ * DESIGN.md §4a (no more than fwav_pool_embed at range sizes 32 and 19).  fwav_pool_embed stays the default because
+ * the reference's embedding is itself up to a few 1e-6 from the exactly rounded one, which fwav_pool_embed returns
+ * at these sizes to within 2^-22. */
+int fwav_embed_exact_supported(int range_size);
+size_t fwav_embed_tables_exact_size(int range_size);
+int fwav_embed_tables_exact(int range_size, double* tab_host);
+int fwav_pool_embed_exact(const float* sig, int64_t n, int tile, int range_size, int step, const double* tab,
+                          float* pool, float* emb, void* emb16, void* workspace, size_t ws_bytes, void* stream);
+/* Test hook (host, no device): scipy.fftpack.dct(x, norm='ortho') for any n with an exact plan, in float32 (dbl = 0)
+ * or float64, through fwav_pool_embed_exact's own DCT code (x and out are doubles). */
+int fwav_debug_dct2_plan(int n, int dbl, const double* x, double* out);
 
 /* ------------------------------------------------------------- energy prune + degenerate queries
  * Replaces the per-range prefix of cpu_worker (fractal.py:598-622) for ranges [q_offset, q_offset + n):
