@@ -42,8 +42,9 @@
 // the DEBUG library only (tools/ab_build.sh adds -DFWAV_DEBUG_API): a product build that sets one stops here, so
 // libfwav.so is always the measured default.
 #if !defined(FWAV_DEBUG_API) && (defined(FWAV_TOPK_ABL) || defined(FWAV_TOPK_APPOFF) || defined(FWAV_TOPK_CAP) || \
-    defined(FWAV_TOPK_CB) || defined(FWAV_TOPK_CENT) || defined(FWAV_TOPK_CENTWIDE) || defined(FWAV_TOPK_CENT_HL) || \
-    defined(FWAV_TOPK_CENT_MINQ) || defined(FWAV_TOPK_CG) || defined(FWAV_TOPK_CHAINS) || \
+    defined(FWAV_TOPK_CB) || defined(FWAV_TOPK_C4G) || defined(FWAV_TOPK_CENT) || defined(FWAV_TOPK_CENT4_MINQ) || \
+    defined(FWAV_TOPK_CENTWIDE) || defined(FWAV_TOPK_CENT_HL) || \
+    defined(FWAV_TOPK_CENT_MINQ) || defined(FWAV_TOPK_CFPMIN) || defined(FWAV_TOPK_CG) || defined(FWAV_TOPK_CHAINS) || \
     defined(FWAV_TOPK_CPDBL) || defined(FWAV_TOPK_CPMIN) || defined(FWAV_TOPK_CSHARE) || defined(FWAV_TOPK_BANDB) || defined(FWAV_TOPK_CVACC) || \
     defined(FWAV_TOPK_CW) || defined(FWAV_TOPK_CWPE) || defined(FWAV_TOPK_DELTA) || defined(FWAV_TOPK_EXGROW) || \
     defined(FWAV_TOPK_EXWPE) || defined(FWAV_TOPK_FIRST) || defined(FWAV_TOPK_G) || defined(FWAV_TOPK_GROW) || \
@@ -723,6 +724,29 @@ struct Topk16SmemT {
   uint32_t fired[FIFO ? NG : 1][kFifo];            // deferred work: ring of fired chunk entries (not in CENT)
   unsigned long long wstat[STATS ? NW : 1][kStats];  // STATS builds only (one row per wave)
 };
+// The per-query rows of the centroid geometry with 4 query sets per wave (1,024 queries per workgroup: S16 / HL
+// passes only): 14 B per query instead of 28, so that two workgroups' 2 × G chunk slots still fit a CU's LDS.  The
+// buffer counts are 16-bit and live here for the whole pass (a set's counts and `kept` are in registers only while
+// its level-2 pairs are scored: they are cold during level 1); the query's table row is rebuilt from the active list
+// where the final pass needs it; `tie` is exact mode's and reads as 0.
+template <int NG, bool STATS, int NW>
+struct Topk16SmemColdT {
+  struct ZeroRow {
+    __device__ uint32_t operator[](int) const { return 0u; }
+  };
+  union {
+    struct {
+      uint16_t cnt[32 * NG];   // entries at the front of the query's buffer (its h = 0 lane's appends)
+      uint16_t cnt1[32 * NG];  // ... and at the back (its h = 1 lane's)
+    };
+    uint16_t cnt01[2 * 32 * NG];  // both, by lane: h · 32·NG + slot
+  };
+  uint16_t kept[32 * NG];  // the buffer's size after its last compaction
+  int ovf[32 * NG];
+  int32_t qpos[32 * NG];
+  ZeroRow tie;
+  unsigned long long wstat[STATS ? NW : 1][kStats];
+};
 
 // Streaming compaction on shl keys (no f32 rescoring, no table loads, no sort): S = the K-th largest shl in the
 // buffer; every exact top-K member has shl ≥ S − 2δ' (K domains have s32 ≥ S − δ'), so keep the band shl > S − 2.5δ'
@@ -798,19 +822,20 @@ __device__ __forceinline__ void compact16_s16(uint64_t* __restrict__ kq, int n0,
 }
 
 // Final pass of query ql (a whole-table item): rescore its two-ended buffer (sm.cnt entries at the front, sm.cnt1 at
-// the back) in exact f32 (sgemv16), sort, emit the top K to `out`.  Whole wave.  Every per-query buffer and
-// counter is owned by one wave, so no cross-wave fences are needed; the wave's own appended stores are drained
-// once (vmcnt(0)), then all key loads and all row loads are issued together (two memory round trips in total).
+// the back) in exact f32 (sgemv16), sort, emit the top K to `out`; qrow = the query's table row.  Whole wave.  Every
+// per-query buffer and counter is owned by one wave, so no cross-wave fences are needed; the wave's own appended
+// stores are drained once (vmcnt(0)), then all key loads and all row loads are issued together (two memory round
+// trips in total).
 template <int C, int E, class SM>
 __device__ __forceinline__ void compact16_e(uint64_t* __restrict__ kq, SM& sm, int ql, int K,
                                             const float* __restrict__ emb, int32_t* __restrict__ out,
                                             const SgemvSplit& sp, int32_t* __restrict__ ties, int32_t qid,
-                                            uint32_t fkey, const FloorCtl& fl) {
+                                            uint32_t fkey, const FloorCtl& fl, int64_t qrow) {
   const int lane = threadIdx.x & 63;
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   const int n0 = sm.cnt[ql];
   const int n = min(n0 + sm.cnt1[ql], C);
-  const float4* qp = reinterpret_cast<const float4*>(emb + sm.qrow[ql] * 16);
+  const float4* qp = reinterpret_cast<const float4*>(emb + qrow * 16);
   uint64_t v[E];
 #pragma unroll
   for (int j = 0; j < E; ++j) {
@@ -876,12 +901,12 @@ template <int C, class SM>
 __device__ __forceinline__ void compact16(uint64_t* __restrict__ kq, SM& sm, int ql, int K,
                                           const float* __restrict__ emb, int32_t* __restrict__ out,
                                           const SgemvSplit& sp, int32_t* __restrict__ ties, int32_t qid,
-                                          uint32_t fkey, const FloorCtl& fl) {
+                                          uint32_t fkey, const FloorCtl& fl, int64_t qrow) {
   const int n = __builtin_amdgcn_readfirstlane(sm.cnt[ql] + sm.cnt1[ql]);
   if (FWAV_TOPK_SMALLSORT && C > 128 && n <= 128)
-    compact16_e<C, 2, SM>(kq, sm, ql, K, emb, out, sp, ties, qid, fkey, fl);
+    compact16_e<C, 2, SM>(kq, sm, ql, K, emb, out, sp, ties, qid, fkey, fl, qrow);
   else
-    compact16_e<C, C / 64, SM>(kq, sm, ql, K, emb, out, sp, ties, qid, fkey, fl);
+    compact16_e<C, C / 64, SM>(kq, sm, ql, K, emb, out, sp, ties, qid, fkey, fl, qrow);
 }
 
 // End of a table piece (split block): no rescoring and no sort here — the piece keeps the entries of its band whose
@@ -1274,7 +1299,9 @@ __device__ __forceinline__ float replay_window(const _Float16* __restrict__ emb1
 #endif
 constexpr int kSeedHalf = FWAV_TOPK_SEEDHALF;
 constexpr int kSeedTiles = (2 * kSeedHalf + 62) / 32 + 1;  // the wave's 32 windows from a tile-aligned base
-template <int MODE>
+// LEAN (the 4-set centroid geometry, whose prologue holds 4 sets' fragments): the tiles' addresses as wave-uniform
+// offsets (wbase is uniform) plus one per-lane index, instead of a 64-bit pointer per tile and lane.
+template <int MODE, bool LEAN = false>
 __device__ __forceinline__ float seed_limit(const _Float16* __restrict__ emb16, int64_t nd, half8 b, int64_t qrow,
                                             int64_t wbase, int K) {
   const int lane = threadIdx.x & 63;
@@ -1287,7 +1314,10 @@ __device__ __forceinline__ float seed_limit(const _Float16* __restrict__ emb16, 
     const int64_t dt = wbase + 32 * t;
     const bool ok = dt >= 0 && dt < nd;
     const int64_t c = ok ? dt / kChunk : 0, tt = ok ? (dt % kChunk) / 32 : 0;
-    afp[t] = reinterpret_cast<const half8*>(emb16 + ((c * 2 + h) * kChunk + col) * 8 + tt * 256);
+    if constexpr (LEAN)
+      afp[t] = reinterpret_cast<const half8*>(emb16 + (c * 2 * kChunk) * 8 + tt * 256) + (h * kChunk + col);
+    else
+      afp[t] = reinterpret_cast<const half8*>(emb16 + ((c * 2 + h) * kChunk + col) * 8 + tt * 256);
     uint32_t m = 0;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
@@ -1476,7 +1506,9 @@ __device__ __forceinline__ void centroid_setup(const _Float16* __restrict__ emb1
 // takes appends; −∞ members make the centroid fire on every tile).  `tight` = false: the worst-case slack alone.
 template <int QS>
 __device__ __forceinline__ int centroid_threshold(const float (&tv)[QS], const CentBound& cb, bool tight) {
-  const int lane = threadIdx.x & 63;
+  int lane = threadIdx.x & 63;
+  // (4 sets: the shuffle addresses computed here, where a limit moved, not held in VGPRs across the whole stream)
+  if constexpr (QS >= 4) asm volatile("" : "+v"(lane));
   const int col = lane & 31;
   const int sj = col % QS, base = (lane & 32) + QS * (col / QS);
   float mn = INFINITY;
@@ -1524,11 +1556,27 @@ if constexpr (FWAV_TOPK_CVACC && NT <= 32) {
     uint64_t co;
     asm("v_addc_co_u32_e64 %0, %1, %2, %2, %3" : "=v"(bits), "=s"(co) : "v"(bits), "s"(m));
   }
+  if constexpr (QS == 4) {
+    // OR over the lanes of each set without shuffle addresses (VGPRs held across the stream): two row rotations
+    // (DPP row_ror:4, :8) leave lane s of every 16-lane row with its row's OR for set s, and the four rows meet in
+    // scalar registers
+    bits |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)bits, 0x124, 0xf, 0xf, false);
+    bits |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)bits, 0x128, 0xf, 0xf, false);
 #pragma unroll
-  for (int off = QS; off < 64; off <<= 1) bits |= (uint32_t)__shfl_xor((int)bits, off);
+    for (int s = 0; s < QS; ++s) {
+      const uint32_t m = (uint32_t)__builtin_amdgcn_readlane((int)bits, s) |
+                         (uint32_t)__builtin_amdgcn_readlane((int)bits, 16 + s) |
+                         (uint32_t)__builtin_amdgcn_readlane((int)bits, 32 + s) |
+                         (uint32_t)__builtin_amdgcn_readlane((int)bits, 48 + s);
+      pend[s] = (uint64_t)(__builtin_bitreverse32(m) >> (32 - NT));
+    }
+  } else {
 #pragma unroll
-  for (int s = 0; s < QS; ++s)
-    pend[s] = (uint64_t)(__builtin_bitreverse32((uint32_t)__builtin_amdgcn_readlane((int)bits, s)) >> (32 - NT));
+    for (int off = QS; off < 64; off <<= 1) bits |= (uint32_t)__shfl_xor((int)bits, off);
+#pragma unroll
+    for (int s = 0; s < QS; ++s)
+      pend[s] = (uint64_t)(__builtin_bitreverse32((uint32_t)__builtin_amdgcn_readlane((int)bits, s)) >> (32 - NT));
+  }
 } else {
 #pragma unroll
   for (int i = 0; i < NT; ++i) {
@@ -1567,13 +1615,20 @@ __global__ __launch_bounds__(64 * W, MODE == kModeEX ? FWAV_TOPK_EXWPE : (CENT ?
   // (Measured and rejected, tools/experiments/ring_and_knobs.patch: a ring of NB slots with LDS ready/free counters
   // instead of the group barrier)
   constexpr int NB = 2;
+  // COLD (the centroid geometry from 4 sets per wave on): the per-set state that level 1 does not read — buffer
+  // counts, `kept`, the list positions — stays in the wave's LDS rows (Topk16SmemColdT), so that level 1 carries only
+  // b[s], thf[s] and the centroid's constants: 4 sets fit the 128-VGPR budget of 4 waves per SIMD with no scratch
+  // access in the stream loop
+  constexpr bool COLD = CENT && QS >= 4;
+  static_assert(!COLD || !EX, "exact mode keeps its tie row (Topk16SmemT)");
+  using SM = std::conditional_t<COLD, Topk16SmemColdT<NG, STATS, W>, Topk16SmemT<NG, STATS, !CENT, W>>;
   struct Lds {
     u32x4 slots[NB * G][512];
-    Topk16SmemT<NG, STATS, !CENT, W> sm;
+    SM sm;
   };
   __shared__ __attribute__((aligned(16))) Lds lds_all;
   u32x4(*slots)[512] = lds_all.slots;
-  Topk16SmemT<NG, STATS, !CENT, W>& sm = lds_all.sm;
+  SM& sm = lds_all.sm;
 
   const int n_active = *n_active_p;
   constexpr int QB = 32 * NG;  // queries per block
@@ -1626,12 +1681,23 @@ __global__ __launch_bounds__(64 * W, MODE == kModeEX ? FWAV_TOPK_EXWPE : (CENT ?
     const int64_t qi = slot_query(block, qslot0 + ql, plan.nb, QB);
     const int32_t q = qi < n_active ? active[qi] : -1;
     const int64_t qrow = (int64_t)(q < 0 ? 0 : q) + q_offset;
-    b[s] = *reinterpret_cast<const half8*>(emb16 + (((qrow >> 8) * 2 + h) * 256 + (qrow & 255)) * 8);
+    // (COLD loads b[s] with the set's seed, below: the seed of set s runs with s + 1 fragments held, not all QS)
+    if constexpr (!COLD)
+      b[s] = *reinterpret_cast<const half8*>(emb16 + (((qrow >> 8) * 2 + h) * 256 + (qrow & 255)) * 8);
     bl[s] = *reinterpret_cast<const half8*>(emb16lo + (((qrow >> 8) * 2 + h) * 256 + (qrow & 255)) * 8);
     upd[s] = (q >= 0 && !(dbg & 1)) ? 1 : 0;
     thf[s] = upd[s] ? -INFINITY : INFINITY;  // slots past n_active never take appends
     qpos[s] = (int32_t)(qi < n_active ? qi : 0);
-    if (h == 0) {
+    if constexpr (COLD) {
+      if (h == 0) {
+        sm.ovf[ql] = 0;
+        sm.qpos[ql] = qpos[s];
+        sm.cnt[ql] = 0;
+        sm.kept[ql] = 0;
+      } else {
+        sm.cnt1[ql] = 0;
+      }
+    } else if (h == 0) {
       sm.ovf[ql] = 0;
       sm.tie[ql] = 0;
       sm.qrow[ql] = qrow;
@@ -1640,7 +1706,8 @@ __global__ __launch_bounds__(64 * W, MODE == kModeEX ? FWAV_TOPK_EXWPE : (CENT ?
     kth[s] = 0ull;
     // relaunch: active = the previous pass's overflow list, whose position qi holds this query's seed (that pass's
     // band limit); seed_shift converts it to this mode's scale (S16 → HL: −(δ + 2δ'); HL → EX: −(δ + 2δ'))
-    inseed[s] = seeds_in != nullptr && q >= 0 ? key2f(seeds_in[qi]) - seed_shift : -INFINITY;
+    // (COLD reads it where it is applied, below: nothing held through the seeds' MFMAs)
+    inseed[s] = !COLD && seeds_in != nullptr && q >= 0 ? key2f(seeds_in[qi]) - seed_shift : -INFINITY;
     if constexpr (EX) {
       const float* qp = emb + qrow * 16;
 #pragma unroll
@@ -1649,27 +1716,46 @@ __global__ __launch_bounds__(64 * W, MODE == kModeEX ? FWAV_TOPK_EXWPE : (CENT ?
   }
 
   // seed the band limits from the queries' own domain windows (tiles from the wave's first query row)
-  if (!(ABL && (dbg & 8192))) {  // ablation 8192: no seed
+  if (COLD || !(ABL && (dbg & 8192))) {  // ablation 8192: no seed
 #pragma unroll
     for (int s = 0; s < QS; ++s) {
       // whole wave (MFMA + shuffles); lanes of unused query slots discard the result
-      const int64_t wbase =
-          (int64_t)((__builtin_amdgcn_readfirstlane((int)sm.qrow[(wave * QS + s) * 32]) - kSeedHalf) >> 5) << 5;
-      const float seed = seed_limit<MODE>(emb16, nd, b[s], sm.qrow[(wave * QS + s) * 32 + col], wbase, K);
-      if (upd[s]) thf[s] = seed;
+      int64_t qrow_s;
+      int qrow_0;  // the set's first slot's row (lane 0 holds it)
+      if constexpr (COLD) {  // (read again from the active list: not held through the other sets' seeds)
+        const int64_t qi = slot_query(block, qslot0 + (wave * QS + s) * 32 + col, plan.nb, QB);
+        const int32_t q = qi < n_active ? active[qi] : -1;
+        qrow_s = (int64_t)(q < 0 ? 0 : q) + q_offset;
+        qrow_0 = __builtin_amdgcn_readfirstlane((int)qrow_s);
+        b[s] = *reinterpret_cast<const half8*>(emb16 + (((qrow_s >> 8) * 2 + h) * 256 + (qrow_s & 255)) * 8);
+        if (ABL && (dbg & 8192)) continue;
+      } else {
+        qrow_s = sm.qrow[(wave * QS + s) * 32 + col];
+        qrow_0 = __builtin_amdgcn_readfirstlane((int)sm.qrow[(wave * QS + s) * 32]);
+      }
+      const int64_t wbase = (int64_t)((qrow_0 - kSeedHalf) >> 5) << 5;
+      const float seed = seed_limit<MODE, COLD>(emb16, nd, b[s], qrow_s, wbase, K);
+      // (COLD keeps no upd[]: a slot that takes no appends has thf = +∞)
+      if (COLD ? thf[s] != INFINITY : upd[s] != 0) thf[s] = seed;
       if (STATS && (dbg & 32768) && gstats != nullptr && h == 0 && upd[s])  // diagnostics: the seeds
         gstats[16 + slot_query(block, qslot0 + (wave * QS + s) * 32 + col, plan.nb, QB)] = __float_as_uint(seed);
     }
   }
   if (seeds_in != nullptr) {
 #pragma unroll
-    for (int s = 0; s < QS; ++s)
-      if (upd[s]) thf[s] = fmaxf(thf[s], inseed[s]);
+    for (int s = 0; s < QS; ++s) {
+      if constexpr (COLD) {
+        const int64_t qi = slot_query(block, qslot0 + (wave * QS + s) * 32 + col, plan.nb, QB);
+        if (qi < n_active) thf[s] = fmaxf(thf[s], key2f(seeds_in[qi]) - seed_shift);  // (+∞ stays +∞)
+      } else if (upd[s]) {
+        thf[s] = fmaxf(thf[s], inseed[s]);
+      }
+    }
   }
   if (fkey != 0u) {
 #pragma unroll
     for (int s = 0; s < QS; ++s)
-      if (upd[s]) thf[s] = fmaxf(thf[s], key2f(fkey));
+      if (COLD || upd[s]) thf[s] = fmaxf(thf[s], key2f(fkey));
   }
   // the query sets this wave works on: set position s holds logical set lid[s] (its slots lid[s]·32 + col, its key
   // buffers and LDS rows) — wave w's own sets w·QS + s (dealing sets to other waves between groups by their recent
@@ -1684,6 +1770,7 @@ __global__ __launch_bounds__(64 * W, MODE == kModeEX ? FWAV_TOPK_EXWPE : (CENT ?
     int ls = lid[0];
 #pragma unroll
     for (int s = 1; s < QS; ++s) ls = sj == s ? lid[s] : ls;
+    if constexpr (COLD) ls = wave * QS + sj;  // (the select chain over 4 sets became a table in scratch)
     centroid_setup<QS>(emb16, [&](int k) -> int64_t {
       const int64_t qi = slot_query(block, qslot0 + ls * 32 + mcol0 + k, plan.nb, QB);
       return qi < n_active ? (int64_t)active[qi] + q_offset : (int64_t)-1;
@@ -1752,8 +1839,11 @@ __global__ __launch_bounds__(64 * W, MODE == kModeEX ? FWAV_TOPK_EXWPE : (CENT ?
         (c_end - c0 <= kWarmChunks) || ((g + 1) % (kWindowGroups * 4 / G) == 0) || (g + 1 == ngroups);
     if (CENT && FWAV_TOPK_CSHARE && share != nullptr) {
 #pragma unroll
-      for (int s = 0; s < QS; ++s)
-        shv[s] = __hip_atomic_load(share + qpos[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      for (int s = 0; s < QS; ++s) {
+        int32_t qp = qpos[s];
+        if constexpr (COLD) qp = sm.qpos[(wave * QS + s) * 32 + col];
+        shv[s] = __hip_atomic_load(share + qp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      }
     }
     const unsigned long long t_b0 = STATS ? __builtin_amdgcn_s_memrealtime() : 0;
     // RAW: own DMA of group g retired, then every wave's (barrier).  WAR: the other half was last read in
@@ -1773,7 +1863,8 @@ __global__ __launch_bounds__(64 * W, MODE == kModeEX ? FWAV_TOPK_EXWPE : (CENT ?
 #pragma unroll
       for (int s = 0; s < QS; ++s) {
         const float t0 = thf[s];
-        if (upd[s] && shv[s] != 0u) thf[s] = fmaxf(thf[s], key2f(shv[s]));
+        // (COLD keeps no upd[]: a slot that takes no appends has thf = +∞, which no limit moves)
+        if ((COLD || upd[s]) && shv[s] != 0u) thf[s] = fmaxf(thf[s], key2f(shv[s]));
         thc_stale |= __ballot(thf[s] != t0) != 0ull;
       }
     }
@@ -1823,6 +1914,21 @@ __global__ __launch_bounds__(64 * W, MODE == kModeEX ? FWAV_TOPK_EXWPE : (CENT ?
         using TMask = uint64_t;  // (32-bit masks for ≤ 32-tile groups: 17.15 vs 16.88 ms)
         TMask pm = (TMask)pend[s];
         TMask pass = 0;  // HL: tiles whose s16 passes the set's stream threshold
+        // COLD: the set's buffer counts come from its LDS rows for the time its marked pairs are scored
+        // (its row index from an opaque lane id: computed here, not held in VGPRs across level 1)
+        int qc_l = 0, kp_l = 0, ci = 0;
+        if constexpr (COLD) {
+          if (pm != 0) {
+            int li = lane;
+            asm volatile("" : "+v"(li));
+            ci = (wave * QS + s) * 32 + (li & 31);
+            qc_l = sm.cnt01[(li >> 5) * 32 * NG + ci];
+            kp_l = sm.kept[ci];
+          }
+        }
+        int& qc = COLD ? qc_l : qcnt[s];
+        int& kp = COLD ? kp_l : kept[s];
+        const int up = COLD ? 1 : upd[s];  // (a slot without appends has thf = +∞)
         while (pm != 0) {
           int t[kCentBatch];
           bool on[kCentBatch];
@@ -1848,10 +1954,8 @@ __global__ __launch_bounds__(64 * W, MODE == kModeEX ? FWAV_TOPK_EXWPE : (CENT ?
             } else {
               const int64_t dt = (int64_t)(cg + (t[u] >> 3)) * kChunk + (t[u] & 7) * 32;
               const float t0 = thf[s];
-              thf[s] = append_tile<C, STATS, Topk16SmemT<NG, STATS, !CENT, W>, MODE>(acc[u], thf[s], qcnt[s], kept[s],
-                                                                                 dt, nd, gkeys, sm, lid[s], K,
-                                                                                 upd[s], stats, sp, emb, qv[s],
-                                                                                 &kth[s], share);
+              thf[s] = append_tile<C, STATS, SM, MODE>(acc[u], thf[s], qc, kp, dt, nd, gkeys, sm, lid[s], K, up, stats,
+                                                       sp, emb, qv[s], &kth[s], share);
               thc_stale |= __ballot(thf[s] != t0) != 0ull;
             }
           }
@@ -1879,12 +1983,16 @@ __global__ __launch_bounds__(64 * W, MODE == kModeEX ? FWAV_TOPK_EXWPE : (CENT ?
               a2 = __builtin_amdgcn_mfma_f32_32x32x16_f16(afl[u], b[s], a2, 0, 0, 0);
               const int64_t dt = (int64_t)(cg + (t[u] >> 3)) * kChunk + (t[u] & 7) * 32;
               const float t0 = thf[s];
-              thf[s] = append_tile<C, STATS, Topk16SmemT<NG, STATS, !CENT, W>, MODE>(a2, thf[s], qcnt[s], kept[s], dt,
-                                                                                 nd, gkeys, sm, lid[s], K,
-                                                                                 upd[s], stats, sp, emb, qv[s],
-                                                                                 &kth[s], share);
+              thf[s] = append_tile<C, STATS, SM, MODE>(a2, thf[s], qc, kp, dt, nd, gkeys, sm, lid[s], K, up, stats, sp,
+                                                       emb, qv[s], &kth[s], share);
               thc_stale |= __ballot(thf[s] != t0) != 0ull;
             }
+          }
+        }
+        if constexpr (COLD) {
+          if (pend[s] != 0ull) {
+            sm.cnt01[h * 32 * NG + ci] = (uint16_t)qc_l;
+            sm.kept[ci] = (uint16_t)kp_l;  // (both lanes of a query hold the same)
           }
         }
       });
@@ -1918,7 +2026,7 @@ __global__ __launch_bounds__(64 * W, MODE == kModeEX ? FWAV_TOPK_EXWPE : (CENT ?
         constexpr int s = decltype(sc)::value;
         if constexpr (!CENT) {
           if (nfired[s] > cur[s].head || cur[s].rem != 0u)
-            thf[s] = replay_window<C, STATS, Topk16SmemT<NG, STATS, !CENT, W>, MODE>(emb16, emb16lo, b[s], bl[s], thf[s],
+            thf[s] = replay_window<C, STATS, SM, MODE>(emb16, emb16lo, b[s], bl[s], thf[s],
                                              qcnt[s], kept[s], cur[s], nfired[s], nd, gkeys, sm, lid[s], K, upd[s],
                                              stats, sp, emb, qv[s], &kth[s], share);
         }
@@ -1933,15 +2041,18 @@ __global__ __launch_bounds__(64 * W, MODE == kModeEX ? FWAV_TOPK_EXWPE : (CENT ?
   }
   const unsigned long long t_final = STATS ? __builtin_amdgcn_s_memrealtime() : 0;
   // the final pass reads the counts from LDS (same wave: program order)
+  if constexpr (!COLD) {  // (COLD: they are there already)
 #pragma unroll
-  for (int s = 0; s < QS; ++s) {
-    if (h == 0)
-      sm.cnt[lid[s] * 32 + col] = qcnt[s];
-    else
-      sm.cnt1[lid[s] * 32 + col] = qcnt[s];
+    for (int s = 0; s < QS; ++s) {
+      if (h == 0)
+        sm.cnt[lid[s] * 32 + col] = qcnt[s];
+      else
+        sm.cnt1[lid[s] * 32 + col] = qcnt[s];
+    }
   }
 
   auto slot_of = [&](int l) {  // the wave's l-th query slot
+    if constexpr (COLD) return wave * QS * 32 + l;
     int ls = lid[0];
 #pragma unroll
     for (int s = 1; s < QS; ++s) ls = (l >> 5) == s ? lid[s] : ls;
@@ -1981,7 +2092,10 @@ __global__ __launch_bounds__(64 * W, MODE == kModeEX ? FWAV_TOPK_EXWPE : (CENT ?
     uint64_t* kq = gkeys + (size_t)qs * C;
     if (lane == 0) FWAV_TRACE(sm.qrow[qs], 3u, (uint32_t)sm.cnt[qs], (uint32_t)sm.ovf[qs], (uint32_t)sm.cnt1[qs]);
     // exact f32 rescoring of the kept band + sort
-    compact16<C>(kq, sm, qs, K, emb, cand + (int64_t)qid * K, sp, ties, qid, fkey, fl);
+    int64_t qrow;
+    if constexpr (COLD) qrow = (int64_t)qid + q_offset;
+    else qrow = sm.qrow[qs];
+    compact16<C>(kq, sm, qs, K, emb, cand + (int64_t)qid * K, sp, ties, qid, fkey, fl, qrow);
     // overflowed: listed for the exact-mode relaunch with its band limit as the seed (same list position)
     if (lane == 0 && sm.ovf[qs]) {
       const int pos = atomicAdd(n_ovf, 1);
@@ -2375,15 +2489,33 @@ constexpr int kWideW = 16, kWideG = 8;
 constexpr int kWideQB = 32 * kWideW;
 constexpr int kCentQS = FWAV_TOPK_CENT > 0 ? FWAV_TOPK_CENT : 4, kCentW = FWAV_TOPK_CW, kCentG = FWAV_TOPK_CG;
 constexpr int kCentQB = 32 * kCentW * kCentQS;
+// the centroid geometry with 4 sets per wave (1,024 queries per workgroup, Topk16SmemColdT): one centroid per 4
+// consecutive queries halves level 1's tiles per query once more
+#ifndef FWAV_TOPK_C4G
+#define FWAV_TOPK_C4G 4  // its chunks per barrier (LDS 80,016 B; cfg2 search 11.69 ms vs 11.94 with 3)
+#endif
+constexpr int kCent4QS = 4, kCent4G = FWAV_TOPK_C4G;
+constexpr int kCent4QB = 32 * kCentW * kCent4QS;
 constexpr int kCentWideQS = 2;  // the centroid filter in the wide geometry: 16 waves × 2 sets, 8 chunks per barrier
 constexpr int kCentWideQB = 32 * kWideW * kCentWideQS;
 #ifdef FWAV_DEBUG_API
 static int g_wide = -1;  // fwav_debug_topk_geometry (debug library only): force base / wide / centroid
+static int g_cent_sets = -1;  // fwav_debug_topk_cent_sets (debug library only): the centroid geometry's sets per wave
 #else
 constexpr int g_wide = -1;
+constexpr int g_cent_sets = -1;
 #endif
 // first-pass geometries
-constexpr int kGeoBase = 0, kGeoWide = 1, kGeoCent = 2, kGeoCentWide = 3;
+// (kGeoCent4, the centroid geometry with 4 sets per wave, is internal: the debug entry points' geometry codes stay
+// 0 … 3, where it is forced as code 2 with fwav_debug_topk_cent_sets(4) and reported by its block layout, geo_code)
+constexpr int kGeoBase = 0, kGeoWide = 1, kGeoCent = 2, kGeoCentWide = 3, kGeoCent4 = 4;
+constexpr int kGeos = 5;
+[[maybe_unused]] constexpr int kGeoCodes = 4;  // (the debug entry points' range)
+// The code the debug entry points report for a first-pass geometry: what fwav_debug_topk_qb and
+// fwav_debug_topk_plan_cover need of it is the block layout, and kGeoCent4's 1,024-query blocks of 32 query groups
+// (two halves of 512) are kGeoCentWide's.
+constexpr int geo_code(int geo) { return geo == kGeoCent4 ? kGeoCentWide : geo; }
+constexpr bool geo_is_cent(int geo) { return geo == kGeoCent || geo == kGeoCent4; }  // 8 waves, two workgroups per CU
 #ifndef FWAV_TOPK_CPDBL
 #define FWAV_TOPK_CPDBL 4  // centroid geometry, blocks on at most half the slots: pieces doubled below this count
 #endif
@@ -2402,7 +2534,10 @@ constexpr int kGeoBase = 0, kGeoWide = 1, kGeoCent = 2, kGeoCentWide = 3;
 #ifndef FWAV_TOPK_CPMIN
 #define FWAV_TOPK_CPMIN 6  // centroid geometry, up to 1.5 rounds of blocks: at least this many table pieces each
 #endif
-constexpr int kCentFloorPieces = 3;  // ... and this many with the speculative floor (profiles/r05/plan_floor_ab*.log)
+#ifndef FWAV_TOPK_CFPMIN
+#define FWAV_TOPK_CFPMIN 3  // ... and this many with the speculative floor (profiles/r05/plan_floor_ab*.log)
+#endif
+constexpr int kCentFloorPieces = FWAV_TOPK_CFPMIN;
 #ifndef FWAV_TOPK_CENT_HL
 #define FWAV_TOPK_CENT_HL 0  // the centroid geometry for hi/lo first passes too (cfg3: 195 vs 180 ms base)
 #endif
@@ -2414,20 +2549,34 @@ constexpr int kCentFloorPieces = 3;  // ... and this many with the speculative f
 // 55,000 4.38 / 4.35 → 3.75), not at 20,672 (2.12 / 2.07 → 2.36: 41 blocks of 512 fill 328 of the 512 slots)
 #define FWAV_TOPK_CENT_MINQ 32768
 #endif
+#ifndef FWAV_TOPK_CENT4_MINQ
+// ... and with 4 sets per wave (kGeoCent4, S16 first passes) from this many queries on.  Same-process A/B against
+// the 2-set geometry, identical candidates (profiles/r08/ab_sizes.log), search ms 2 sets → 4 sets: 330,750 queries
+// 13.30 → 11.81, 262,144 10.61 → 9.44, 220,000 9.69 → 9.04, 165,375 7.28 → 7.19, 82,688 4.13 → 3.85, 41,344 (81
+// blocks of 512 → 41 of 1,024 on 512 slots) 2.46 → 2.95.  (82,688 keeps 2 sets: DESIGN §10.)
+#define FWAV_TOPK_CENT4_MINQ 131072
+#endif
 static int first_geometry(int64_t nd, int64_t max_q) {
-  if (g_wide >= 0) return g_wide;
+  // (4 sets are instantiated for S16 passes only: a hi/lo first pass runs kGeoCent whatever g_cent_sets asks for; a
+  // forced kGeoCent is the 2-set geometry unless g_cent_sets says 4)
+  const bool s16 = first_mode(nd) == kModeS16;
+  if (g_wide >= 0) return g_wide == kGeoCent && g_cent_sets == 4 && s16 ? kGeoCent4 : g_wide;
   if (nd > (int64_t)FWAV_TOPK_WIDE_MIN)
     return FWAV_TOPK_CENTWIDE && max_q >= (int64_t)FWAV_TOPK_CENT_MINQ ? kGeoCentWide : kGeoWide;
   const bool cent = FWAV_TOPK_CENT > 0 && max_q >= (int64_t)FWAV_TOPK_CENT_MINQ &&
                     (FWAV_TOPK_CENT_HL || first_mode(nd) == kModeS16);
+  const bool four = g_cent_sets < 0 ? max_q >= (int64_t)FWAV_TOPK_CENT4_MINQ : g_cent_sets == 4;
+  if (cent && four && s16) return kGeoCent4;
   return cent ? kGeoCent : kGeoBase;
 }
 static int geometry_qb(int geo) {
-  return geo == kGeoWide ? kWideQB : (geo == kGeoCent ? kCentQB : (geo == kGeoCentWide ? kCentWideQB : k16QB));
+  return geo == kGeoWide ? kWideQB
+                         : (geo == kGeoCent ? kCentQB
+                                            : (geo == kGeoCentWide ? kCentWideQB : (geo == kGeoCent4 ? kCent4QB : k16QB)));
 }
 
 static void topk_device_slots(int geo, int& cus, int& per_cu) {
-  static int cs[4][kMaxDev] = {{0}}, ws[4][kMaxDev] = {{0}};
+  static int cs[kGeos][kMaxDev] = {{0}}, ws[kGeos][kMaxDev] = {{0}};
   const int dev = current_device();
   int& c = cs[geo][dev];
   int& w = ws[geo][dev];
@@ -2439,6 +2588,9 @@ static void topk_device_slots(int geo, int& cus, int& per_cu) {
         : geo == kGeoCent
             ? hipOccupancyMaxActiveBlocksPerMultiprocessor(
                   &w, k_sim_topk_f16<k16Cap, false, kModeS16, kCentW, kCentG, kCentQS, true>, 64 * kCentW, 0)
+        : geo == kGeoCent4
+            ? hipOccupancyMaxActiveBlocksPerMultiprocessor(
+                  &w, k_sim_topk_f16<k16Cap, false, kModeS16, kCentW, kCent4G, kCent4QS, true>, 64 * kCentW, 0)
         : geo == kGeoCentWide
             ? hipOccupancyMaxActiveBlocksPerMultiprocessor(
                   &w, k_sim_topk_f16<k16Cap, false, kModeHL, kWideW, kWideG, kCentWideQS, true>, 64 * kWideW, 0)
@@ -2447,7 +2599,7 @@ static void topk_device_slots(int geo, int& cus, int& per_cu) {
     if (!(hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && occ == hipSuccess &&
           c > 0 && w > 0)) {
       c = 256;  // MI355X: 256 CUs × 2 base (1 wide) workgroups
-      w = (geo == kGeoBase || geo == kGeoCent) ? 2 : 1;
+      w = (geo == kGeoBase || geo_is_cent(geo)) ? 2 : 1;
     }
   }
   cus = c;
@@ -2480,7 +2632,7 @@ static void host_plan_for(int64_t max_q, int64_t nd, int geo, int& rt, int& P, i
       // 65,536: 5.29 → 4.83 with 4 instead of 2; 20,672: 2.25 → 2.08 with 6, block-major before)
       rt = (int)nb;
       int64_t p = slots / nb;
-      if (FWAV_TOPK_PMAJOR && p < (geo == kGeoCent ? FWAV_TOPK_CPDBL : 4)) p *= 2;
+      if (FWAV_TOPK_PMAJOR && p < (geo_is_cent(geo) ? FWAV_TOPK_CPDBL : 4)) p *= 2;
       P = (int)(p < kPlanMaxPieces ? p : kPlanMaxPieces);
     } else if (FWAV_TOPK_PMAJOR && 2 * nb <= 3 * slots) {
       // up to 1.5 rounds of blocks: every block in max(3, ⌊2·slots / nb⌋) pieces, piece-major — later rounds start
@@ -2496,7 +2648,7 @@ static void host_plan_for(int64_t max_q, int64_t nd, int geo, int& rt, int& P, i
       // With the speculative floor (§3.1b of DESIGN) no piece starts cold, and fewer, longer pieces pay: cfg2 in 3 / 4 /
       // 6 pieces 15.72 / 15.95 / 16.02 ms, 165,375 queries 8.66 / 8.89 / 8.75 (profiles/r05/plan_floor_ab*.log)
       const bool fl = floored < 0 ? floor_by_default(max_q, nd) : floored != 0;
-      const int64_t pmin = (geo == kGeoCent) ? (fl ? kCentFloorPieces : FWAV_TOPK_CPMIN) : 3;
+      const int64_t pmin = geo_is_cent(geo) ? (fl ? kCentFloorPieces : FWAV_TOPK_CPMIN) : 3;
       if (p < pmin) p = pmin;
       P = (int)(p < kPlanMaxPieces ? p : kPlanMaxPieces);
     } else {
@@ -2889,10 +3041,11 @@ static size_t f16_keys_bytes(int64_t max_q, int64_t nd) {
     const size_t n2 = (size_t)make_plan(q, rt2, P2, k16QB).items() * k16QB;
     items_q = n2 > items_q ? n2 : items_q;
   }
-  for (int geo = 0; geo < 8; ++geo) {  // each geometry with and without the floor (a debug knob may switch it)
+  for (int gf = 0; gf < 2 * kGeos; ++gf) {  // each geometry with and without the floor (a debug knob may switch it)
     int rt, P;
-    host_plan_for(q, nd, geo & 3, rt, P, geo >> 2);
-    const int qb = geometry_qb(geo & 3);
+    const int geo = gf % kGeos;
+    host_plan_for(q, nd, geo, rt, P, gf / kGeos);
+    const int qb = geometry_qb(geo);
     const size_t n = (size_t)make_plan(q, rt, P, qb).items() * qb;
     items_q = n > items_q ? n : items_q;
   }
@@ -3031,6 +3184,11 @@ static int launch_topk(const float* emb, const _Float16* emb16, int64_t nd, cons
               emb16, emb, nd, act, nact, q_offset, K, cand, gkeys, ovf1, n_ovf1, share, nullptr, 0.0f, rt, P,
               dbg & 65535, stats, sp, ties, fl);
         done = true;
+      } else if (!done && diag && stats_first && g == kGeoCent4) {
+        k_sim_topk_f16<k16Cap, true, kModeS16, kCentW, kCent4G, kCent4QS, true><<<pl.items(), 64 * kCentW, 0, st>>>(
+            emb16, emb, nd, act, nact, q_offset, K, cand, gkeys, ovf1, n_ovf1, share, nullptr, 0.0f, rt, P,
+            dbg & 65535, stats, sp, ties, fl);
+        done = true;
       } else if (!done && diag && stats_first) {
         if (mode1 == kModeHL) FWAV_FIRST(kModeHL, true, dbg & 65535, stats);
         else FWAV_FIRST(kModeS16, true, dbg & 65535, stats);
@@ -3044,6 +3202,8 @@ static int launch_topk(const float* emb, const _Float16* emb16, int64_t nd, cons
         } else if (g == kGeoCent) {
           if (mode1 == kModeHL) FWAV_FIRST_GEO(kModeHL, kCentW, kCentG, kCentQS, true);
           else FWAV_FIRST_GEO(kModeS16, kCentW, kCentG, kCentQS, true);
+        } else if (g == kGeoCent4) {  // (S16 only: first_geometry)
+          FWAV_FIRST_GEO(kModeS16, kCentW, kCent4G, kCent4QS, true);
         } else if (g == kGeoCentWide) {
           if (mode1 == kModeHL) FWAV_FIRST_GEO(kModeHL, kWideW, kWideG, kCentWideQS, true);
           else FWAV_FIRST_GEO(kModeS16, kWideW, kWideG, kCentWideQS, true);
@@ -3069,6 +3229,8 @@ static int launch_topk(const float* emb, const _Float16* emb16, int64_t nd, cons
           if (mode1 == kModeHL) FWAV_MERGE(kWideQB, true); else FWAV_MERGE(kWideQB, false);
         } else if (g == kGeoCent) {
           if (mode1 == kModeHL) FWAV_MERGE(kCentQB, true); else FWAV_MERGE(kCentQB, false);
+        } else if (g == kGeoCent4) {
+          FWAV_MERGE(kCent4QB, false);
         } else if (g == kGeoCentWide) {
           if (mode1 == kModeHL) FWAV_MERGE(kCentWideQB, true); else FWAV_MERGE(kCentWideQB, false);
         } else {
@@ -3087,7 +3249,7 @@ static int launch_topk(const float* emb, const _Float16* emb16, int64_t nd, cons
     // profiles/r06/active_order/cfg3_*.log)
     const int32_t* order = active;
     const int32_t* n_order = n_active;
-    if (geo == kGeoCent) {
+    if (geo_is_cent(geo)) {
       int32_t* const ord = reinterpret_cast<int32_t*>(wb + lay.order);
       int32_t* const n_ord = reinterpret_cast<int32_t*>(wb + lay.n_order);
       order_active(active, n_active, max_q, reinterpret_cast<uint32_t*>(wb + lay.order_bits),
@@ -3258,8 +3420,16 @@ int fwav_debug_topk_mode(int mode) {
 // Diagnostic override of the first pass's geometry: 0 = base (8 waves, 256 queries per workgroup), 1 = wide (16
 // waves, 512 queries, one workgroup per CU), −1 = by table size (default).  Both return the same candidates.
 int fwav_debug_topk_geometry(int wide) {
-  FWAV_CHECK_ARG(wide >= -1 && wide <= 3, FWAV_ERR_ARG, "fwav_debug_topk_geometry: outside [-1, 3]");
+  FWAV_CHECK_ARG(wide >= -1 && wide < kGeoCodes, FWAV_ERR_ARG, "fwav_debug_topk_geometry: outside [-1, 3]");
   g_wide = wide;
+  return FWAV_OK;
+}
+
+// Diagnostic override of the centroid geometry's query sets per wave (include/fwav_debug.h): 2, 4, −1 = by the query
+// count (default).
+int fwav_debug_topk_cent_sets(int sets) {
+  FWAV_CHECK_ARG(sets == -1 || sets == 2 || sets == 4, FWAV_ERR_ARG, "fwav_debug_topk_cent_sets: not -1, 2 or 4");
+  g_cent_sets = sets;
   return FWAV_OK;
 }
 
@@ -3292,12 +3462,14 @@ int fwav_debug_topk_floor_pieces(int p2) {
 // A query of a whole-table block or a query half must be counted once, one of a block split into P table pieces P
 // times.  *items = the launch's grid.
 int fwav_debug_topk_plan_cover(int64_t n, int rt, int pieces, int wide, int32_t* count, int64_t* items) {
-  FWAV_CHECK_ARG(n >= 0 && count && items && wide >= 0 && wide <= 3 &&
+  FWAV_CHECK_ARG(n >= 0 && count && items && wide >= 0 && wide < kGeoCodes &&
                      (pieces == -1 || (pieces >= 1 && pieces <= kMaxPieces)), FWAV_ERR_ARG,
                  "fwav_debug_topk_plan_cover: bad args");  // (any plan's pieces: the floor's later passes take 16)
-  const int geo = wide;  // 0 base, 1 wide, 2 centroid, 3 centroid wide
-  const int W = (geo == kGeoWide || geo == kGeoCentWide) ? kWideW : (geo == kGeoCent ? kCentW : k16Waves);
-  const int sets = geo == kGeoCent ? kCentQS : (geo == kGeoCentWide ? kCentWideQS : k16Sets), qb = 32 * W * sets;
+  const int geo = wide;  // 0 base, 1 wide, 2 centroid, 3 centroid wide (and the 4-set centroid geometry's layout)
+  const int W = (geo == kGeoWide || geo == kGeoCentWide) ? kWideW : (geo_is_cent(geo) ? kCentW : k16Waves);
+  const int sets = geo == kGeoCent ? kCentQS
+                                   : (geo == kGeoCentWide ? kCentWideQS : (geo == kGeoCent4 ? kCent4QS : k16Sets)),
+            qb = 32 * W * sets;
   const TopkPlan pl = make_plan(n, rt, pieces, qb);
   *items = pl.items();
   for (int64_t it = 0; it < pl.items(); ++it) {
@@ -3341,7 +3513,7 @@ int fwav_debug_topk_plan_info(int64_t max_q, int64_t nd, int32_t* info, int64_t*
   int rt, P;
   host_plan_for(max_q, nd, geo, rt, P);
   const TopkPlan pl = make_plan(max_q, rt, P, geometry_qb(geo));
-  info[0] = geo;
+  info[0] = geo_code(geo);
   info[1] = first_mode(nd);
   info[2] = pl.halves ? -1 : pl.P;
   blocks[0] = pl.F;
@@ -3350,8 +3522,9 @@ int fwav_debug_topk_plan_info(int64_t max_q, int64_t nd, int32_t* info, int64_t*
   return FWAV_OK;
 }
 
-// Queries per block (one workgroup's query slots) of first-pass geometry geo (0 base, 1 wide, 2 centroid).
-int64_t fwav_debug_topk_qb(int geo) { return geo >= 0 && geo <= 3 ? geometry_qb(geo) : -1; }
+// Queries per block (one workgroup's query slots) of first-pass geometry geo (0 base, 1 wide, 2 centroid, 3 centroid
+// wide).
+int64_t fwav_debug_topk_qb(int geo) { return geo >= 0 && geo < kGeoCodes ? geometry_qb(geo) : -1; }
 
 // Byte offsets of the fp16 search's workspace regions for max_q queries over nd domains (K ≤ 64), in the order of
 // TopkLayout: keys, share, ovf2, n_ovf2, seeds2, ovf1, n_ovf1, seeds1, miss, n_miss, miss2, n_miss2, floor_key,

@@ -80,6 +80,7 @@ DEBUG_SIGNATURES = {
     "fwav_debug_topk_plan_cover": (I32, [I64, I32, I32, I32, P, P]),
     "fwav_debug_topk_mode": (I32, [I32]),
     "fwav_debug_topk_geometry": (I32, [I32]),
+    "fwav_debug_topk_cent_sets": (I32, [I32]),
     "fwav_debug_topk_plan_info": (I32, [I64, I64, P, P]),
     "fwav_debug_topk_piece_chunks": (I32, [I64, I64, I64, P, P]),
     "fwav_debug_topk_qb": (I64, [I32]),
@@ -184,6 +185,7 @@ class debug_library:
         d.fwav_debug_topk_plan(-1, 1)
         d.fwav_debug_topk_mode(-1)
         d.fwav_debug_topk_geometry(-1)
+        d.fwav_debug_topk_cent_sets(-1)
         d.fwav_debug_topk_floor(-1, 0.0)
         d.fwav_debug_topk_floor_pieces(0)
         d.fwav_debug_topk_tail(-1)

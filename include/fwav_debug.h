@@ -54,6 +54,13 @@ int fwav_debug_topk_mode(int mode);
  * default).  All return the same candidates.  Re-query
  * fwav_sim_topk_workspace_size afterwards. */
 int fwav_debug_topk_geometry(int wide);
+/* Diagnostic override of the centroid pre-filter's query sets per wave (geometry 2, forced or chosen): 2 = sets of
+ * 2 × 32 (512 queries per workgroup), 4 = sets of 4 × 32 (1,024 queries per workgroup; fp16-band first passes only,
+ * a hi/lo one runs 2), −1 = the default: 2 when geometry 2 is forced, else by the query count.  With 4 sets
+ * fwav_debug_topk_plan_info reports geometry 3, whose block layout (1,024 queries, 32 query groups) it shares: that is
+ * the code fwav_debug_topk_qb and fwav_debug_topk_plan_cover take for it.  Same candidates.  Re-query
+ * fwav_sim_topk_workspace_size afterwards. */
+int fwav_debug_topk_cent_sets(int sets);
 /* Queries per block (one workgroup's query slots) of first-pass geometry geo (0 base, 1 wide, 2 centroid,
  * 3 centroid wide); −1 for another geo. */
 int64_t fwav_debug_topk_qb(int geo);
