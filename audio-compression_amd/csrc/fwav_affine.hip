@@ -398,7 +398,7 @@ __device__ __forceinline__ void pair_errors(const float* __restrict__ R, int rs,
   }
 }
 
-template <int RS>
+template <int RS, int ED = 16>
 __global__ __launch_bounds__(256) void k_tie_check(const float* __restrict__ ranges, int rs,
                                                    const int32_t* __restrict__ cand, int K,
                                                    const float* __restrict__ pool, const float* __restrict__ emb,
@@ -419,9 +419,13 @@ __global__ __launch_bounds__(256) void k_tie_check(const float* __restrict__ ran
     const int32_t ci = has ? cand[(int64_t)row * K + lane] : -1;
     const int32_t di = ci < 0 ? 0 : ci;
     // exact scores (the search's order) → runs of equal scores → run id per position
-    const float* qp = emb + ((int64_t)row + q_offset) * 16;
-    const float* dp = emb + (int64_t)di * 16;
-    const float sc = sgemv16([&](int k) { return dp[k]; }, [&](int k) { return qp[k]; }, sgemv_kind((uint32_t)di, sp));
+    const float* qp = emb + ((int64_t)row + q_offset) * ED;
+    const float* dp = emb + (int64_t)di * ED;
+    float sc;
+    if constexpr (ED == 16)
+      sc = sgemv16([&](int k) { return dp[k]; }, [&](int k) { return qp[k]; }, sgemv_kind((uint32_t)di, sp));
+    else
+      sc = sgemv_dim<ED>([&](int k) { return dp[k]; }, [&](int k) { return qp[k]; }, sgemv_kind((uint32_t)di, sp));
     const float prev = __shfl_up(sc, 1);
     const bool start = has && (lane == 0 || prev != sc);
     const uint64_t le = lane == 63 ? ~0ull : ((2ull << lane) - 1ull);
@@ -548,26 +552,54 @@ int fwav_debug_gather_rows(const float* table, int64_t n_rows, int rs, int64_t n
   return FWAV_OK;
 }
 
-int fwav_tie_check(const float* ranges, int64_t n_ranges, int rs, const int32_t* cand, int K, const float* pool,
-                   int64_t nd, const float* emb, int64_t q_offset, int blas_threads, const int32_t* ties,
-                   int64_t max_ties, int exact_sets, int32_t* resolve, void* stream) {
+static int tie_check_launch(const char* what, const float* ranges, int64_t n_ranges, int rs, const int32_t* cand,
+                            int K, const float* pool, int64_t nd, const float* emb, int emb_dim, int64_t q_offset,
+                            int blas_threads, const int32_t* ties, int64_t max_ties, int exact_sets, int32_t* resolve,
+                            void* stream) {
   FWAV_CHECK_ARG(ranges && cand && pool && emb && ties && resolve && n_ranges >= 0 && rs >= 1 && K >= 1 && nd >= 1 &&
                      nd < (int64_t)0x7fffffff && max_ties >= 0 && blas_threads >= 1 && blas_threads <= 4096,
-                 FWAV_ERR_ARG, "fwav_tie_check: bad args");
-  FWAV_CHECK_ARG(rs <= kMaxPairwise, FWAV_ERR_SHAPE, "fwav_tie_check: rs > %d", kMaxPairwise);
+                 FWAV_ERR_ARG, "%s: bad args", what);
+  FWAV_CHECK_ARG(rs <= kMaxPairwise, FWAV_ERR_SHAPE, "%s: rs > %d", what, kMaxPairwise);
   hipStream_t st = (hipStream_t)stream;
   (void)hipMemsetAsync(resolve, 0, sizeof(int32_t), st);
   if (max_ties == 0) return FWAV_OK;
-  const SgemvSplit sp = make_sgemv_split(nd, blas_threads);
+  const SgemvSplit sp = make_sgemv_split_dim(nd, blas_threads, emb_dim);
   const int64_t grid = cdiv(max_ties, 4);
-  switch (rs) {
-    case 4: k_tie_check<4><<<grid, 256, 0, st>>>(ranges, rs, cand, K, pool, emb, q_offset, sp, ties, exact_sets, resolve); break;
-    case 8: k_tie_check<8><<<grid, 256, 0, st>>>(ranges, rs, cand, K, pool, emb, q_offset, sp, ties, exact_sets, resolve); break;
-    case 16: k_tie_check<16><<<grid, 256, 0, st>>>(ranges, rs, cand, K, pool, emb, q_offset, sp, ties, exact_sets, resolve); break;
-    default: k_tie_check<0><<<grid, 256, 0, st>>>(ranges, rs, cand, K, pool, emb, q_offset, sp, ties, exact_sets, resolve);
+#define FWAV_TIE(RSV, EDV)                                                                                         \
+  k_tie_check<RSV, EDV><<<grid, 256, 0, st>>>(ranges, rs, cand, K, pool, emb, q_offset, sp, ties, exact_sets, resolve)
+  if (emb_dim == 32) {
+    switch (rs) {
+      case 4: FWAV_TIE(4, 32); break;
+      case 8: FWAV_TIE(8, 32); break;
+      case 16: FWAV_TIE(16, 32); break;
+      default: FWAV_TIE(0, 32);
+    }
+  } else {
+    switch (rs) {
+      case 4: FWAV_TIE(4, 16); break;
+      case 8: FWAV_TIE(8, 16); break;
+      case 16: FWAV_TIE(16, 16); break;
+      default: FWAV_TIE(0, 16);
+    }
   }
-  FWAV_LAUNCH_CHECK("fwav_tie_check");
+#undef FWAV_TIE
+  FWAV_LAUNCH_CHECK(what);
   return FWAV_OK;
+}
+
+int fwav_tie_check(const float* ranges, int64_t n_ranges, int rs, const int32_t* cand, int K, const float* pool,
+                   int64_t nd, const float* emb, int64_t q_offset, int blas_threads, const int32_t* ties,
+                   int64_t max_ties, int exact_sets, int32_t* resolve, void* stream) {
+  return tie_check_launch("fwav_tie_check", ranges, n_ranges, rs, cand, K, pool, nd, emb, 16, q_offset, blas_threads,
+                          ties, max_ties, exact_sets, resolve, stream);
+}
+
+int fwav_tie_check_dim(const float* ranges, int64_t n_ranges, int rs, const int32_t* cand, int K, const float* pool,
+                       int64_t nd, const float* emb, int emb_dim, int64_t q_offset, int blas_threads,
+                       const int32_t* ties, int64_t max_ties, int exact_sets, int32_t* resolve, void* stream) {
+  FWAV_CHECK_ARG(emb_dim == 32, FWAV_ERR_ARG, "fwav_tie_check_dim: emb_dim %d (only 32 is supported)", emb_dim);
+  return tie_check_launch("fwav_tie_check_dim", ranges, n_ranges, rs, cand, K, pool, nd, emb, emb_dim, q_offset,
+                          blas_threads, ties, max_ties, exact_sets, resolve, stream);
 }
 
 int fwav_affine(const float* ranges, int64_t nr, int rs, const int32_t* cand, int K, const float* pool, int64_t nd,

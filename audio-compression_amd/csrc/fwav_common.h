@@ -174,6 +174,43 @@ __device__ __forceinline__ float sgemv16(const D& d, const Q& q, int kind = 0) {
   return ((l[0] + l[4]) + (l[1] + l[5])) + ((l[2] + l[6]) + (l[3] + l[7]));
 }
 
+// The same three kernels on rows of D columns (D a multiple of 8; emb_dim = 32, fwav_topk_wide.hip), pinned against
+// numpy for D = 16, 24, 32 and 64 (tests/test_embdim_cpu.py):
+//   kind 0: 8 lanes, each a chain of D/8 fmas l_j = fma(d[j+8b], q[j+8b], l_j), b = 0 … D/8 − 1, from 0; sgemv16's fold;
+//   kind 1: 4 lanes of rounded products added in index order, l[k % 4] += p_k, then (l0 + l1) + (l2 + l3);
+//   kind 2: 8 lanes l[k % 8] += p_k, sgemv16's fold.
+// OpenBLAS stays on one thread while D·nd < 460,800 (m·n of the gemv), so the split depends on the width.
+__host__ inline SgemvSplit make_sgemv_split_dim(int64_t nd, int threads, int dim) {
+  const int64_t T = ((int64_t)dim * nd < 460800 || threads < 1) ? 1 : threads;
+  return SgemvSplit{(uint32_t)(nd / T), (uint32_t)(nd % T)};
+}
+template <int D, class DF, class QF>
+__host__ __device__ __forceinline__ float sgemv_dim(const DF& d, const QF& q, int kind = 0) {
+  static_assert(D % 8 == 0 && D >= 8, "rows of whole 8-lane steps");
+  if (kind == 0) {
+    float l[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) l[j] = 0.0f;
+#pragma unroll
+    for (int b = 0; b < D / 8; ++b)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) l[j] = __builtin_fmaf(d(j + 8 * b), q(j + 8 * b), l[j]);
+    return ((l[0] + l[4]) + (l[1] + l[5])) + ((l[2] + l[6]) + (l[3] + l[7]));
+  }
+  if (kind == 1) {
+    float l[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int k = 0; k < D; ++k) l[k & 3] = l[k & 3] + d(k) * q(k);
+    return (l[0] + l[1]) + (l[2] + l[3]);
+  }
+  float l[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) l[j] = 0.0f;
+#pragma unroll
+  for (int k = 0; k < D; ++k) l[k & 7] = l[k & 7] + d(k) * q(k);
+  return ((l[0] + l[4]) + (l[1] + l[5])) + ((l[2] + l[6]) + (l[3] + l[7]));
+}
+
 // np.clip(x, -c, c) keeps NaN (comparisons false).
 __device__ __forceinline__ float clip_sym(float x, float c) { return x < -c ? -c : (x > c ? c : x); }
 

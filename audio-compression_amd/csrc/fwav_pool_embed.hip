@@ -100,7 +100,41 @@ __device__ __forceinline__ void store_emb16(_Float16* __restrict__ emb16, int64_
   }
 }
 
-template <int RS>
+// The fp16 table of the wide search (fwav_topk_wide.hip; emb_dim = 16·NS): row d's high parts only, tiled
+// [chunk of 256][16-column step s][half h][256][8], so that a chunk is one contiguous block of 256·16·NS halfs and a
+// lane's MFMA fragment of step s (columns 16s + 8h …) is one 16-byte read.  Rounds to nearest even, keeps subnormals.
+template <int NS>
+__device__ __forceinline__ void store_embh(_Float16* __restrict__ embh, int64_t d, const float (&out)[16 * NS]) {
+  typedef _Float16 half8 __attribute__((ext_vector_type(8)));
+  const int64_t c = d >> 8, j = d & 255;
+#pragma unroll
+  for (int sh = 0; sh < 2 * NS; ++sh) {
+    half8 vh;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) vh[e] = (_Float16)out[8 * sh + e];
+    *reinterpret_cast<half8*>(embh + ((c * 2 * NS + sh) * 256 + j) * 8) = vh;
+  }
+}
+
+// ddot of a vector with itself as numpy's f64 norm evaluates it (OpenBLAS ddot, Haswell/SkylakeX kernel) for n ≤ 16
+// values v(0 … n−1): below 16 a sequential fma chain; at 16 four lanes l[i % 4] += v_i·v_i (product and add rounded
+// separately), folded (l0 + l2) + (l1 + l3).  (From 32 values on the order is another one: emb_dim stops at 32.)
+template <class V>
+__host__ __device__ __forceinline__ double ddot_self(const V& v, int n) {
+  if (n < 16) {
+    double s2 = 0.0;
+    for (int j = 0; j < n; ++j) s2 = __builtin_fma(v(j), v(j), s2);
+    return s2;
+  }
+  double l[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+  for (int i = 0; i < 16; ++i) l[i & 3] = l[i & 3] + v(i) * v(i);
+  return (l[0] + l[2]) + (l[1] + l[3]);
+}
+
+// H = coefficients per head: 8 (emb_dim 16; emb16 = the two-part table of fwav_topk.hip) or 16 (emb_dim 32; emb16 =
+// the wide search's table, store_embh).  tab layout (f64): tonal rows [H][rs] then transient rows [H][rs].
+template <int RS, int H = 8>
 __global__ void k_embed(const float* __restrict__ src, int64_t nd, int rs, int64_t a, int64_t b,
                         const double* __restrict__ tab, float* __restrict__ pool_out, float* __restrict__ emb,
                         _Float16* __restrict__ emb16) {
@@ -108,19 +142,19 @@ __global__ void k_embed(const float* __restrict__ src, int64_t nd, int rs, int64
   if (d >= nd) return;
   const int n = RS > 0 ? RS : rs;
   const float* xs = src + d * a;
-  const int take = n - 1 < 8 ? n - 1 : 8;
-  const int tk = n < 8 ? n : 8;
+  const int take = n - 1 < H ? n - 1 : H;
+  const int tk = n < H ? n : H;
   const double* tt = tab;
-  const double* td = tab + 8 * n;
-  float e[8];
-  double t[8];
-  float tf[8];
+  const double* td = tab + H * n;
+  float e[H];
+  double t[H];
+  float tf[H];
   if constexpr (RS == 4 || RS == 8 || RS == 16) {
     // exact path: scipy's pocketfft DCTs and numpy's / OpenBLAS's norm orders (see the file header)
     DctK<float, RS> kf;
     DctK<double, RS> kd;
-    dct_load(kf, tab + 16 * RS);
-    dct_load(kd, tab + 16 * RS + dct_block(RS));
+    dct_load(kf, tab + 2 * H * RS);
+    dct_load(kd, tab + 2 * H * RS + dct_block(RS));
     float x[RS];
 #pragma unroll
     for (int i = 0; i < RS; ++i) x[i] = xs[i * b];
@@ -133,26 +167,30 @@ __global__ void k_embed(const float* __restrict__ src, int64_t nd, int rs, int64
     for (int i = 0; i < RS; ++i) c[i] = x[i];
     dct2_ortho<float, RS>(c, kf);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) e[j] = j < take ? (float)((double)c[j + 1 < RS ? j + 1 : 0] * kd.w[j + 1 < RS ? j + 1 : 0]) : 0.0f;
+    for (int j = 0; j < H; ++j) e[j] = j < take ? (float)((double)c[j + 1 < RS ? j + 1 : 0] * kd.w[j + 1 < RS ? j + 1 : 0]) : 0.0f;
     double acc = 0.0;  // sdot: f32 products, f64 sum in index order, f32 result
 #pragma unroll
-    for (int j = 0; j < 8; ++j) acc = acc + (double)(e[j] * e[j]);
+    for (int j = 0; j < H; ++j) acc = acc + (double)(e[j] * e[j]);
     const float nrm = sqrtf((float)acc);
     if (nrm > 1e-8f) {
 #pragma unroll
-      for (int j = 0; j < 8; ++j) e[j] = e[j] / nrm;
+      for (int j = 0; j < H; ++j) e[j] = e[j] / nrm;
     }
     double dv[RS];
 #pragma unroll
     for (int i = 0; i < RS; ++i) dv[i] = (double)(i == 0 ? x[0] - x[0] : x[i] - x[i - 1]) * kd.w[i];
     dct2_ortho<double, RS>(dv, kd);
     double s2 = 0.0;  // ddot, n < 16: fma chain
+    if constexpr (H == 16 && RS == 16) {
+      s2 = ddot_self([&](int j) { return dv[j]; }, 16);
+    } else {
 #pragma unroll
-    for (int j = 0; j < 8; ++j)
-      if (j < tk) s2 = __builtin_fma(dv[j < RS ? j : 0], dv[j < RS ? j : 0], s2);
+      for (int j = 0; j < H; ++j)
+        if (j < tk) s2 = __builtin_fma(dv[j < RS ? j : 0], dv[j < RS ? j : 0], s2);
+    }
     const double nrmd = sqrt(s2);
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
+    for (int j = 0; j < H; ++j) {
       double v = j < tk ? dv[j < RS ? j : 0] : 0.0;
       if (nrmd > 1e-8) v = v / nrmd;
       tf[j] = (float)v;
@@ -161,47 +199,54 @@ __global__ void k_embed(const float* __restrict__ src, int64_t nd, int rs, int64
     if (pool_out) {
       for (int i = 0; i < n; ++i) pool_out[d * n + i] = xs[i * b];
     }
-    for (int j = 0; j < 8; ++j) {
+    for (int j = 0; j < H; ++j) {
       double acc = 0.0;
       for (int i = 0; i < n; ++i) acc += tt[j * n + i] * (double)xs[i * b];
       e[j] = j < take ? (float)acc : 0.0f;
     }
-    for (int j = 0; j < 8; ++j) t[j] = 0.0;
+    for (int j = 0; j < H; ++j) t[j] = 0.0;
     for (int i = 0; i < n; ++i) {
       float xi = xs[i * b];
       float xp = i == 0 ? xi : xs[(i - 1) * b];
       double dd = (double)(xi - xp);
-      for (int j = 0; j < 8; ++j) t[j] += td[j * n + i] * dd;
+      for (int j = 0; j < H; ++j) t[j] += td[j * n + i] * dd;
     }
     double acc = 0.0;  // tonal norm in sdot order
-    for (int j = 0; j < 8; ++j) acc = acc + (double)(e[j] * e[j]);
+    for (int j = 0; j < H; ++j) acc = acc + (double)(e[j] * e[j]);
     const float nrm = sqrtf((float)acc);
     if (nrm > 1e-8f) {
-      for (int j = 0; j < 8; ++j) e[j] = e[j] / nrm;
+      for (int j = 0; j < H; ++j) e[j] = e[j] / nrm;
     }
-    double s2d = 0.0;  // transient: ddot fma chain over the tk kept coefficients
-    for (int j = 0; j < 8; ++j)
-      if (j < tk) s2d = __builtin_fma(t[j], t[j], s2d);
+    double s2d = 0.0;  // transient: ddot over the tk kept coefficients (an fma chain below 16 of them)
+    if (H == 16 && tk == 16) {
+      s2d = ddot_self([&](int j) { return t[j]; }, 16);
+    } else {
+      for (int j = 0; j < H; ++j)
+        if (j < tk) s2d = __builtin_fma(t[j], t[j], s2d);
+    }
     const double nd64 = sqrt(s2d);
-    for (int j = 0; j < 8; ++j) {
+    for (int j = 0; j < H; ++j) {
       double v = j < tk ? t[j] : 0.0;
       if (nd64 > 1e-8) v = v / nd64;
       tf[j] = (float)v;
     }
   }
-  // concatenation [tonal 8 | transient tk] then zero pad to 16 (multi_head_embedding :170-175)
-  float out[16];
+  // concatenation [tonal H | transient tk] then zero pad to 2·H (multi_head_embedding :170-175)
+  float out[2 * H];
 #pragma unroll
-  for (int j = 0; j < 16; ++j) out[j] = 0.0f;
+  for (int j = 0; j < 2 * H; ++j) out[j] = 0.0f;
 #pragma unroll
-  for (int j = 0; j < 8; ++j) out[j] = e[j];
+  for (int j = 0; j < H; ++j) out[j] = e[j];
 #pragma unroll
-  for (int j = 0; j < 8; ++j)
-    if (j < tk) out[8 + j] = tf[j];
-  float4* o4 = reinterpret_cast<float4*>(emb + d * 16);
+  for (int j = 0; j < H; ++j)
+    if (j < tk) out[H + j] = tf[j];
+  float4* o4 = reinterpret_cast<float4*>(emb + d * 2 * H);
 #pragma unroll
-  for (int j = 0; j < 4; ++j) o4[j] = make_float4(out[4 * j], out[4 * j + 1], out[4 * j + 2], out[4 * j + 3]);
-  if (emb16 != nullptr) store_emb16(emb16, nd, d, out);
+  for (int j = 0; j < H / 2; ++j) o4[j] = make_float4(out[4 * j], out[4 * j + 1], out[4 * j + 2], out[4 * j + 3]);
+  if (emb16 != nullptr) {
+    if constexpr (H == 8) store_emb16(emb16, nd, d, out);
+    else store_embh<H / 8>(emb16, d, out);
+  }
 }
 
 // Domain-embedding rows → the fp16 tables of the search (store_emb16), for embeddings produced elsewhere.
@@ -219,10 +264,10 @@ __global__ __launch_bounds__(kPoolThreads) void k_emb16(const float* __restrict_
   store_emb16(emb16, nd, d, out);
 }
 
-template <int RS>
+template <int RS, int H = 8>
 static void launch_embed(const float* src, int64_t nd, int rs, int64_t a, int64_t b, const double* tab,
                          float* pool_out, float* emb, _Float16* emb16, hipStream_t st) {
-  k_embed<RS><<<cdiv(nd, kPoolThreads), kPoolThreads, 0, st>>>(src, nd, rs, a, b, tab, pool_out, emb, emb16);
+  k_embed<RS, H><<<cdiv(nd, kPoolThreads), kPoolThreads, 0, st>>>(src, nd, rs, a, b, tab, pool_out, emb, emb16);
 }
 
 // pocketfft's sincos_2pibyn<T>(n)[idx] (Thigh = double for float and double): a two-level table of octant-reduced
@@ -519,6 +564,75 @@ static void launch_embed_exact(const float* src, int64_t nd, int64_t a, int64_t 
                                                                          emb16);
 }
 
+// The pool stage of every fwav_pool_embed* entry point: block means (S in the workspace) when the block length is a
+// multiple of the step, else every pool element on its own.  Returns where the embedding kernel reads row d, element k
+// (src[d·a + k·b]) and whether it still has to write the pool rows.
+struct PoolSrc {
+  const float* src;
+  int64_t a, b;
+  float* pool_out;
+};
+static PoolSrc pool_stage(const float* sig, int64_t nd, int rs, int step, int bl, float* pool, float* S,
+                          hipStream_t st) {
+  if (bl % step == 0) {
+    const int64_t m = bl / step;
+    const int64_t ns = (nd - 1) + (int64_t)(rs - 1) * m + 1;
+    const int64_t g = cdiv(ns, kPoolThreads);
+    if (bl == 256) k_block_means<256><<<g, kPoolThreads, 0, st>>>(sig, ns, step, bl, S);
+    else if (bl == 128) k_block_means<128><<<g, kPoolThreads, 0, st>>>(sig, ns, step, bl, S);
+    else k_block_means<0><<<g, kPoolThreads, 0, st>>>(sig, ns, step, bl, S);
+    return PoolSrc{S, 1, m, pool};
+  }
+  k_domain_pool<<<cdiv(nd * rs, kPoolThreads), kPoolThreads, 0, st>>>(sig, nd, rs, step, bl, pool);
+  return PoolSrc{pool, rs, 1, nullptr};
+}
+
+// Domain-embedding rows (emb_dim = 16·NS) → the wide search's fp16 table (store_embh).
+template <int NS>
+__global__ __launch_bounds__(kPoolThreads) void k_embh(const float* __restrict__ emb, int64_t nd,
+                                                       _Float16* __restrict__ embh) {
+  const int64_t d = (int64_t)blockIdx.x * kPoolThreads + threadIdx.x;
+  if (d >= nd) return;
+  float out[16 * NS];
+  const float4* p = reinterpret_cast<const float4*>(emb + d * 16 * NS);
+#pragma unroll
+  for (int j = 0; j < 4 * NS; ++j) {
+    const float4 v = p[j];
+    out[4 * j] = v.x; out[4 * j + 1] = v.y; out[4 * j + 2] = v.z; out[4 * j + 3] = v.w;
+  }
+  store_embh<NS>(embh, d, out);
+}
+
+// Zeroes rows nd … of the last chunk of the wide search's table (every step and half), so that they score 0.
+static void zero_embh_tail(_Float16* embh, int64_t nd, int dim, hipStream_t st) {
+  if ((nd & 255) == 0) return;
+  const int64_t c = nd >> 8, j0 = nd & 255;
+  for (int sh = 0; sh < dim / 8; ++sh)
+    (void)hipMemsetAsync(embh + ((c * (dim / 8) + sh) * 256 + j0) * 8, 0, (size_t)(256 - j0) * 8 * sizeof(_Float16), st);
+}
+
+// fwav_embed_tables' content for heads of H coefficients: the f64 matrices (tonal H rows, transient H rows of rs;
+// zero rows past the coefficients a range size has) and, for rs = 4, 8, 16, pocketfft's constants in both precisions.
+static void embed_tables_fill(int rs, int H, double* tab) {
+  const double pi = 3.14159265358979323846;
+  const int n = rs;
+  auto w = [&](int i) { return n == 1 ? 1.0 : 1.0 + (double)i / (double)(n - 1); };  // np.linspace(1, 2, n)
+  auto c = [&](int k, int i) {
+    double f = k == 0 ? std::sqrt(1.0 / n) : std::sqrt(2.0 / n);
+    return f * std::cos(pi * k * (2.0 * i + 1.0) / (2.0 * n));
+  };
+  const int take = n - 1 < H ? n - 1 : H;
+  const int tk = n < H ? n : H;
+  for (int j = 0; j < H; ++j)
+    for (int i = 0; i < n; ++i) tab[j * n + i] = j < take ? c(j + 1, i) * w(j + 1) : 0.0;
+  for (int j = 0; j < H; ++j)
+    for (int i = 0; i < n; ++i) tab[H * n + j * n + i] = j < tk ? c(j, i) * w(i) : 0.0;
+  if (rs == 4 || rs == 8 || rs == 16) {
+    dct_constants(rs, false, tab + 2 * H * rs);
+    dct_constants(rs, true, tab + 2 * H * rs + dct_block(rs));
+  }
+}
+
 static bool exact_routes_fixed(int rs) { return rs == 4 || rs == 8 || rs == 16; }
 
 }  // namespace fwav
@@ -537,23 +651,7 @@ size_t fwav_embed_tables_size(int rs) {
 
 int fwav_embed_tables(int rs, double* tab) {
   FWAV_CHECK_ARG(rs >= 1 && rs <= kMaxPairwise && tab, FWAV_ERR_ARG, "fwav_embed_tables: bad args");
-  const double pi = 3.14159265358979323846;
-  const int n = rs;
-  auto w = [&](int i) { return n == 1 ? 1.0 : 1.0 + (double)i / (double)(n - 1); };  // np.linspace(1, 2, n)
-  auto c = [&](int k, int i) {
-    double f = k == 0 ? std::sqrt(1.0 / n) : std::sqrt(2.0 / n);
-    return f * std::cos(pi * k * (2.0 * i + 1.0) / (2.0 * n));
-  };
-  const int take = n - 1 < 8 ? n - 1 : 8;
-  const int tk = n < 8 ? n : 8;
-  for (int j = 0; j < 8; ++j)
-    for (int i = 0; i < n; ++i) tab[j * n + i] = j < take ? c(j + 1, i) * w(j + 1) : 0.0;
-  for (int j = 0; j < 8; ++j)
-    for (int i = 0; i < n; ++i) tab[8 * n + j * n + i] = j < tk ? c(j, i) * w(i) : 0.0;
-  if (rs == 4 || rs == 8 || rs == 16) {
-    dct_constants(rs, false, tab + 16 * rs);
-    dct_constants(rs, true, tab + 16 * rs + dct_block(rs));
-  }
+  embed_tables_fill(rs, 8, tab);
   return FWAV_OK;
 }
 
@@ -678,24 +776,12 @@ int fwav_pool_embed(const float* sig, int64_t n, int tile, int rs, int step, con
                  "fwav_pool_embed: block length out of range");
   hipStream_t st = (hipStream_t)stream;
   const int64_t nd = (n - tile) / step + 1;
-  const float* src;
-  int64_t a, b;
-  float* pool_out;
-  if (bl % step == 0) {
-    FWAV_CHECK_ARG(ws_bytes >= fwav_pool_workspace_size(n, tile, rs, step) && workspace, FWAV_ERR_WORKSPACE,
-                   "fwav_pool_embed: workspace too small");
-    const int64_t m = bl / step;
-    const int64_t ns = (nd - 1) + (int64_t)(rs - 1) * m + 1;
-    float* S = (float*)workspace;
-    const int64_t g = cdiv(ns, kPoolThreads);
-    if (bl == 256) k_block_means<256><<<g, kPoolThreads, 0, st>>>(sig, ns, step, bl, S);
-    else if (bl == 128) k_block_means<128><<<g, kPoolThreads, 0, st>>>(sig, ns, step, bl, S);
-    else k_block_means<0><<<g, kPoolThreads, 0, st>>>(sig, ns, step, bl, S);
-    src = S; a = 1; b = m; pool_out = pool;
-  } else {
-    k_domain_pool<<<cdiv(nd * rs, kPoolThreads), kPoolThreads, 0, st>>>(sig, nd, rs, step, bl, pool);
-    src = pool; a = rs; b = 1; pool_out = nullptr;
-  }
+  FWAV_CHECK_ARG(bl % step != 0 || (ws_bytes >= fwav_pool_workspace_size(n, tile, rs, step) && workspace),
+                 FWAV_ERR_WORKSPACE, "fwav_pool_embed: workspace too small");
+  const PoolSrc ps = pool_stage(sig, nd, rs, step, bl, pool, (float*)workspace, st);
+  const float* src = ps.src;
+  const int64_t a = ps.a, b = ps.b;
+  float* pool_out = ps.pool_out;
   _Float16* e16 = (_Float16*)emb16;
   if (e16 != nullptr && (nd & 255) != 0) {
     // zero the padded tail of the last chunk (both halves of both tables)
@@ -732,24 +818,12 @@ int fwav_pool_embed_exact(const float* sig, int64_t n, int tile, int rs, int ste
   FWAV_CHECK_ARG(bl >= 1 && bl <= kMaxPairwise, FWAV_ERR_SHAPE, "fwav_pool_embed_exact: block length out of range");
   hipStream_t st = (hipStream_t)stream;
   const int64_t nd = (n - tile) / step + 1;
-  const float* src;
-  int64_t a, b;
-  float* pool_out;
-  if (bl % step == 0) {
-    FWAV_CHECK_ARG(ws_bytes >= fwav_pool_workspace_size(n, tile, rs, step) && workspace, FWAV_ERR_WORKSPACE,
-                   "fwav_pool_embed_exact: workspace too small");
-    const int64_t m = bl / step;
-    const int64_t ns = (nd - 1) + (int64_t)(rs - 1) * m + 1;
-    float* S = (float*)workspace;
-    const int64_t g = cdiv(ns, kPoolThreads);
-    if (bl == 256) k_block_means<256><<<g, kPoolThreads, 0, st>>>(sig, ns, step, bl, S);
-    else if (bl == 128) k_block_means<128><<<g, kPoolThreads, 0, st>>>(sig, ns, step, bl, S);
-    else k_block_means<0><<<g, kPoolThreads, 0, st>>>(sig, ns, step, bl, S);
-    src = S; a = 1; b = m; pool_out = pool;
-  } else {
-    k_domain_pool<<<cdiv(nd * rs, kPoolThreads), kPoolThreads, 0, st>>>(sig, nd, rs, step, bl, pool);
-    src = pool; a = rs; b = 1; pool_out = nullptr;
-  }
+  FWAV_CHECK_ARG(bl % step != 0 || (ws_bytes >= fwav_pool_workspace_size(n, tile, rs, step) && workspace),
+                 FWAV_ERR_WORKSPACE, "fwav_pool_embed_exact: workspace too small");
+  const PoolSrc ps = pool_stage(sig, nd, rs, step, bl, pool, (float*)workspace, st);
+  const float* src = ps.src;
+  const int64_t a = ps.a, b = ps.b;
+  float* pool_out = ps.pool_out;
   _Float16* e16 = (_Float16*)emb16;
   if (e16 != nullptr && (nd & 255) != 0) {
     // zero the padded tail of the last chunk (both halves of both tables)
@@ -766,6 +840,62 @@ int fwav_pool_embed_exact(const float* sig, int64_t n, int tile, int rs, int ste
   else if (rs <= 48) launch_embed_exact<48>(src, nd, a, b, tab, plan, pool_out, emb, e16, st);
   else launch_embed_exact<64>(src, nd, a, b, tab, plan, pool_out, emb, e16, st);
   FWAV_LAUNCH_CHECK("fwav_pool_embed_exact");
+  return FWAV_OK;
+}
+
+// ---- emb_dim = 32 (heads of 16 coefficients; the wide search's table, fwav_topk_wide.hip)
+size_t fwav_embh_elems(int64_t nd, int emb_dim) {
+  return emb_dim == 32 && nd > 0 ? (size_t)(((nd + 255) / 256) * 256 * emb_dim) : 0;
+}
+
+int fwav_embh_from_emb(const float* emb, int64_t nd, int emb_dim, void* embh, void* stream) {
+  FWAV_CHECK_ARG(emb_dim == 32, FWAV_ERR_ARG, "fwav_embh_from_emb: emb_dim %d (only 32 is supported)", emb_dim);
+  FWAV_CHECK_ARG(emb && embh && nd > 0, FWAV_ERR_ARG, "fwav_embh_from_emb: bad args");
+  hipStream_t st = (hipStream_t)stream;
+  zero_embh_tail((_Float16*)embh, nd, emb_dim, st);
+  k_embh<2><<<cdiv(nd, kPoolThreads), kPoolThreads, 0, st>>>(emb, nd, (_Float16*)embh);
+  FWAV_LAUNCH_CHECK("fwav_embh_from_emb");
+  return FWAV_OK;
+}
+
+size_t fwav_embed_tables_dim_size(int rs, int emb_dim) {
+  if (emb_dim != 32 || rs < 1) return 0;
+  return (size_t)emb_dim * rs + (exact_routes_fixed(rs) ? 2 * (size_t)dct_block(rs) : 0);
+}
+
+int fwav_embed_tables_dim(int rs, int emb_dim, double* tab) {
+  FWAV_CHECK_ARG(emb_dim == 32, FWAV_ERR_ARG, "fwav_embed_tables_dim: emb_dim %d (only 32 is supported)", emb_dim);
+  FWAV_CHECK_ARG(rs >= 1 && rs <= kMaxPairwise && tab, FWAV_ERR_ARG, "fwav_embed_tables_dim: bad args");
+  embed_tables_fill(rs, emb_dim / 2, tab);
+  return FWAV_OK;
+}
+
+// fwav_pool_embed with rows of emb_dim = 32 columns: [tonal: min(16, rs − 1) values, zero-padded to 16][transient:
+// min(16, rs) values][zeros to 32].  tab: device copy of fwav_embed_tables_dim(rs, 32); embh (optional):
+// f16[fwav_embh_elems(nd, 32)], rows past nd zeroed here.
+int fwav_pool_embed_dim(const float* sig, int64_t n, int tile, int rs, int step, int emb_dim, const double* tab,
+                        float* pool, float* emb, void* embh, void* workspace, size_t ws_bytes, void* stream) {
+  FWAV_CHECK_ARG(emb_dim == 32, FWAV_ERR_ARG, "fwav_pool_embed_dim: emb_dim %d (only 32 is supported)", emb_dim);
+  FWAV_CHECK_ARG(sig && pool && emb && tab && tile > 0 && rs > 0 && step > 0, FWAV_ERR_ARG,
+                 "fwav_pool_embed_dim: bad args");
+  FWAV_CHECK_ARG(n >= tile, FWAV_ERR_SHAPE, "fwav_pool_embed_dim: n < tile");
+  const int bl = tile / rs;
+  FWAV_CHECK_ARG(bl >= 1 && bl <= kMaxPairwise && rs <= kMaxPairwise, FWAV_ERR_SHAPE,
+                 "fwav_pool_embed_dim: block length out of range");
+  FWAV_CHECK_ARG(bl % step != 0 || (ws_bytes >= fwav_pool_workspace_size(n, tile, rs, step) && workspace),
+                 FWAV_ERR_WORKSPACE, "fwav_pool_embed_dim: workspace too small");
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t nd = (n - tile) / step + 1;
+  const PoolSrc ps = pool_stage(sig, nd, rs, step, bl, pool, (float*)workspace, st);
+  _Float16* eh = (_Float16*)embh;
+  if (eh != nullptr) zero_embh_tail(eh, nd, emb_dim, st);
+  switch (rs) {
+    case 4: launch_embed<4, 16>(ps.src, nd, rs, ps.a, ps.b, tab, ps.pool_out, emb, eh, st); break;
+    case 8: launch_embed<8, 16>(ps.src, nd, rs, ps.a, ps.b, tab, ps.pool_out, emb, eh, st); break;
+    case 16: launch_embed<16, 16>(ps.src, nd, rs, ps.a, ps.b, tab, ps.pool_out, emb, eh, st); break;
+    default: launch_embed<0, 16>(ps.src, nd, rs, ps.a, ps.b, tab, ps.pool_out, emb, eh, st); break;
+  }
+  FWAV_LAUNCH_CHECK("fwav_pool_embed_dim");
   return FWAV_OK;
 }
 

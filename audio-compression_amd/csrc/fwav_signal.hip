@@ -292,7 +292,7 @@ __global__ void k_energy_chain(const float* __restrict__ bufsum, int64_t nb, flo
 //                       0..min(K,nd)−1
 //   otherwise         → appended to `active` for the similarity search
 // RS > 0: compile-time range size (row in registers, unrolled pairwise sum); RS == 0: runtime rs.
-template <int RS>
+template <int RS, int ED = 16>
 __global__ void k_prune(const float* __restrict__ ranges, int64_t nr, int64_t q_offset, int rs_rt, float thr,
                         int fast_mode, const float* __restrict__ emb, int64_t nd, int k,
                         const int32_t* __restrict__ zero_cand, int32_t* __restrict__ cand,
@@ -323,9 +323,9 @@ __global__ void k_prune(const float* __restrict__ ranges, int64_t nr, int64_t q_
   bool pruned = fast_mode && (mean_sq < thr);
   bool zero = true;
   if (!pruned) {
-    const float4* q = reinterpret_cast<const float4*>(emb + (i + q_offset) * 16);
+    const float4* q = reinterpret_cast<const float4*>(emb + (i + q_offset) * ED);
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
+    for (int j = 0; j < ED / 4; ++j) {
       float4 v = q[j];
       zero = zero && v.x == 0.0f && v.y == 0.0f && v.z == 0.0f && v.w == 0.0f;
     }
@@ -430,31 +430,56 @@ int fwav_weighted_energy(const float* ranges, int64_t n, float* sum, void* works
   return FWAV_OK;
 }
 
+// prune_dim: emb rows of emb_dim columns (16: fwav_prune; 32: fwav_prune_dim).
+static int prune_launch(const char* what, const float* ranges, int64_t nr, int64_t q_offset, int rs, float prune_thr,
+                        int fast_mode, const float* emb, int64_t nd, int emb_dim, int k, const int32_t* zero_cand,
+                        int32_t* cand, int32_t* active, int32_t* n_active, void* stream) {
+  FWAV_CHECK_ARG(ranges && emb && cand && active && n_active && k > 0, FWAV_ERR_ARG, "%s: bad args", what);
+  FWAV_CHECK_ARG(q_offset >= 0 && q_offset + nr <= nd, FWAV_ERR_SHAPE,
+                 "%s: query rows past n_domains (query rows are domain rows, quirk Q1)", what);
+  FWAV_CHECK_ARG(rs <= kMaxPairwise, FWAV_ERR_SHAPE, "%s: rs too large", what);
+  hipStream_t st = (hipStream_t)stream;
+  (void)hipMemsetAsync(n_active, 0, sizeof(int32_t), st);
+  if (nr == 0) return FWAV_OK;
+  const int64_t grid = cdiv(nr, kSignalThreads);
+#define FWAV_PRUNE(RSV, EDV)                                                                                  \
+  k_prune<RSV, EDV><<<grid, kSignalThreads, 0, st>>>(ranges, nr, q_offset, rs, prune_thr, fast_mode, emb, nd, k, \
+                                                     zero_cand, cand, active, n_active)
+  if (emb_dim == 32) {
+    switch (rs) {
+      case 4: FWAV_PRUNE(4, 32); break;
+      case 8: FWAV_PRUNE(8, 32); break;
+      case 16: FWAV_PRUNE(16, 32); break;
+      default: FWAV_PRUNE(0, 32);
+    }
+  } else {
+    switch (rs) {
+      case 4: FWAV_PRUNE(4, 16); break;
+      case 8: FWAV_PRUNE(8, 16); break;
+      case 16: FWAV_PRUNE(16, 16); break;
+      default: FWAV_PRUNE(0, 16);
+    }
+  }
+#undef FWAV_PRUNE
+  FWAV_LAUNCH_CHECK(what);
+  return FWAV_OK;
+}
+
 // Ranges [q_offset, q_offset + nr) of the whole signal: ranges/cand/active are shard-local (row i), the
 // query embedding of local range i is emb row q_offset + i.
 int fwav_prune(const float* ranges, int64_t nr, int64_t q_offset, int rs, float prune_thr, int fast_mode,
                const float* emb, int64_t nd, int k, const int32_t* zero_cand, int32_t* cand, int32_t* active,
                int32_t* n_active, void* stream) {
-  FWAV_CHECK_ARG(ranges && emb && cand && active && n_active && k > 0, FWAV_ERR_ARG, "fwav_prune: bad args");
-  FWAV_CHECK_ARG(q_offset >= 0 && q_offset + nr <= nd, FWAV_ERR_SHAPE,
-                 "fwav_prune: query rows past n_domains (query rows are domain rows, quirk Q1)");
-  FWAV_CHECK_ARG(rs <= kMaxPairwise, FWAV_ERR_SHAPE, "fwav_prune: rs too large");
-  hipStream_t st = (hipStream_t)stream;
-  (void)hipMemsetAsync(n_active, 0, sizeof(int32_t), st);
-  if (nr == 0) return FWAV_OK;
-  const int64_t grid = cdiv(nr, kSignalThreads);
-  switch (rs) {
-#define FWAV_PRUNE(RSV)                                                                                      \
-  k_prune<RSV><<<grid, kSignalThreads, 0, st>>>(ranges, nr, q_offset, rs, prune_thr, fast_mode, emb, nd, k,     \
-                                                zero_cand, cand, active, n_active)
-    case 4: FWAV_PRUNE(4); break;
-    case 8: FWAV_PRUNE(8); break;
-    case 16: FWAV_PRUNE(16); break;
-    default: FWAV_PRUNE(0);
-#undef FWAV_PRUNE
-  }
-  FWAV_LAUNCH_CHECK("fwav_prune");
-  return FWAV_OK;
+  return prune_launch("fwav_prune", ranges, nr, q_offset, rs, prune_thr, fast_mode, emb, nd, 16, k, zero_cand, cand,
+                      active, n_active, stream);
+}
+
+int fwav_prune_dim(const float* ranges, int64_t nr, int64_t q_offset, int rs, float prune_thr, int fast_mode,
+                   const float* emb, int64_t nd, int emb_dim, int k, const int32_t* zero_cand, int32_t* cand,
+                   int32_t* active, int32_t* n_active, void* stream) {
+  FWAV_CHECK_ARG(emb_dim == 32, FWAV_ERR_ARG, "fwav_prune_dim: emb_dim %d (only 32 is supported)", emb_dim);
+  return prune_launch("fwav_prune_dim", ranges, nr, q_offset, rs, prune_thr, fast_mode, emb, nd, emb_dim, k,
+                      zero_cand, cand, active, n_active, stream);
 }
 
 }  // extern "C"

@@ -29,71 +29,71 @@ constexpr int kScoreThreads = 256;
 constexpr int kScoreQ = 32;            // queries per k_scores_batch pass (q vectors in LDS)
 constexpr size_t kLargeBudget = size_t(1) << 30;  // score-row workspace budget (bytes)
 
-__device__ __forceinline__ float score_chain(const float (&e)[16], const float* __restrict__ q, int kind) {
-  return sgemv16([&](int k) { return e[k]; }, [&](int k) { return q[k]; }, kind);
+// One exact score of a row of ED columns: sgemv16 (emb_dim 16) or its D-column form (fwav_common.h sgemv_dim).
+template <int ED>
+__device__ __forceinline__ float score_chain(const float (&e)[ED], const float* __restrict__ q, int kind) {
+  if constexpr (ED == 16) return sgemv16([&](int k) { return e[k]; }, [&](int k) { return q[k]; }, kind);
+  else return sgemv_dim<ED>([&](int k) { return e[k]; }, [&](int k) { return q[k]; }, kind);
+}
+template <int ED>
+__device__ __forceinline__ void load_row(float (&e)[ED], const float* __restrict__ emb, int64_t d) {
+  const float4* p = reinterpret_cast<const float4*>(emb + d * ED);
+#pragma unroll
+  for (int j = 0; j < ED / 4; ++j) {
+    const float4 v = p[j];
+    e[4 * j] = v.x; e[4 * j + 1] = v.y; e[4 * j + 2] = v.z; e[4 * j + 3] = v.w;
+  }
 }
 
 // S[j·nd + d] = score(domain d, query active[qb + j]) for j < B (rows of queries past n_active untouched).
+template <int ED>
 __global__ __launch_bounds__(kScoreThreads) void k_scores_batch(const float* __restrict__ emb, int64_t nd,
                                                                 const int32_t* __restrict__ active,
                                                                 const int32_t* __restrict__ n_active_p,
                                                                 int64_t qb, int B, int64_t q_offset, SgemvSplit sp,
                                                                 float* __restrict__ S) {
-  __shared__ float qv[kScoreQ][16];
+  __shared__ float qv[kScoreQ][ED];
   const int n_active = *n_active_p;
   if (qb >= n_active) return;
   const int nb = (int)min<int64_t>(B, n_active - qb);
   const int64_t d = (int64_t)blockIdx.x * kScoreThreads + threadIdx.x;
-  float e[16];
-  if (d < nd) {
-    const float4* p = reinterpret_cast<const float4*>(emb + d * 16);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float4 v = p[j];
-      e[4 * j] = v.x; e[4 * j + 1] = v.y; e[4 * j + 2] = v.z; e[4 * j + 3] = v.w;
-    }
-  }
+  float e[ED];
+  if (d < nd) load_row<ED>(e, emb, d);
   for (int j0 = 0; j0 < nb; j0 += kScoreQ) {
     const int m = min(kScoreQ, nb - j0);
     __syncthreads();
-    for (int t = threadIdx.x; t < m * 16; t += kScoreThreads) {
-      const int64_t q = (int64_t)active[qb + j0 + t / 16] + q_offset;
-      qv[t / 16][t % 16] = emb[q * 16 + t % 16];
+    for (int t = threadIdx.x; t < m * ED; t += kScoreThreads) {
+      const int64_t q = (int64_t)active[qb + j0 + t / ED] + q_offset;
+      qv[t / ED][t % ED] = emb[q * ED + t % ED];
     }
     __syncthreads();
     if (d < nd) {
       const int kind = sgemv_kind((uint32_t)d, sp);
-      for (int j = 0; j < m; ++j) S[(int64_t)(j0 + j) * nd + d] = score_chain(e, qv[j], kind);
+      for (int j = 0; j < m; ++j) S[(int64_t)(j0 + j) * nd + d] = score_chain<ED>(e, qv[j], kind);
     }
   }
 }
 
 // S[i·nd + d] = score(domain d, query row q_offset + rows[i]), i < n_rows (fwav_score_rows).
+template <int ED>
 __global__ __launch_bounds__(kScoreThreads) void k_score_rows(const float* __restrict__ emb, int64_t nd,
                                                               const int32_t* __restrict__ rows, int n_rows,
                                                               int64_t q_offset, SgemvSplit sp, float* __restrict__ S) {
-  __shared__ float qv[kScoreQ][16];
+  __shared__ float qv[kScoreQ][ED];
   const int64_t d = (int64_t)blockIdx.x * kScoreThreads + threadIdx.x;
-  float e[16];
-  if (d < nd) {
-    const float4* p = reinterpret_cast<const float4*>(emb + d * 16);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float4 v = p[j];
-      e[4 * j] = v.x; e[4 * j + 1] = v.y; e[4 * j + 2] = v.z; e[4 * j + 3] = v.w;
-    }
-  }
+  float e[ED];
+  if (d < nd) load_row<ED>(e, emb, d);
   const int kind = d < nd ? sgemv_kind((uint32_t)d, sp) : 0;
   for (int j0 = 0; j0 < n_rows; j0 += kScoreQ) {
     const int m = min(kScoreQ, n_rows - j0);
     __syncthreads();
-    for (int t = threadIdx.x; t < m * 16; t += kScoreThreads) {
-      const int64_t q = (int64_t)rows[j0 + t / 16] + q_offset;
-      qv[t / 16][t % 16] = emb[q * 16 + t % 16];
+    for (int t = threadIdx.x; t < m * ED; t += kScoreThreads) {
+      const int64_t q = (int64_t)rows[j0 + t / ED] + q_offset;
+      qv[t / ED][t % ED] = emb[q * ED + t % ED];
     }
     __syncthreads();
     if (d < nd)
-      for (int j = 0; j < m; ++j) S[(int64_t)(j0 + j) * nd + d] = score_chain(e, qv[j], kind);
+      for (int j = 0; j < m; ++j) S[(int64_t)(j0 + j) * nd + d] = score_chain<ED>(e, qv[j], kind);
   }
 }
 
@@ -309,27 +309,47 @@ int64_t large_batch(int64_t nd, int64_t max_q) {
 
 size_t large_workspace_bytes(int64_t nd, int64_t max_q) { return (size_t)large_batch(nd, max_q) * nd * 4; }
 
-int launch_topk_large(const float* emb, int64_t nd, const int32_t* active, const int32_t* n_active, int64_t max_q,
-                      int64_t q_offset, int K, int32_t* cand, float* S, SgemvSplit sp, int32_t* ties, hipStream_t st) {
+// dim = the embedding rows' width: 16, or 32 (fwav_sim_topk_dim / fwav_score_rows_dim, fwav_topk_wide.hip).
+int launch_topk_large_dim(const float* emb, int64_t nd, int dim, const int32_t* active, const int32_t* n_active,
+                          int64_t max_q, int64_t q_offset, int K, int32_t* cand, float* S, SgemvSplit sp,
+                          int32_t* ties, hipStream_t st) {
   const int64_t B = large_batch(nd, max_q);
   for (int64_t qb = 0; qb < max_q; qb += B) {
-    k_scores_batch<<<cdiv(nd, kScoreThreads), kScoreThreads, 0, st>>>(emb, nd, active, n_active, qb, (int)B,
-                                                                       q_offset, sp, S);
+    if (dim == 32)
+      k_scores_batch<32><<<cdiv(nd, kScoreThreads), kScoreThreads, 0, st>>>(emb, nd, active, n_active, qb, (int)B,
+                                                                             q_offset, sp, S);
+    else
+      k_scores_batch<16><<<cdiv(nd, kScoreThreads), kScoreThreads, 0, st>>>(emb, nd, active, n_active, qb, (int)B,
+                                                                             q_offset, sp, S);
     k_select<<<B, kSelThreads, 0, st>>>(S, nd, active, n_active, qb, K, cand, ties);
   }
   FWAV_LAUNCH_CHECK("fwav_sim_topk (large K)");
   return FWAV_OK;
 }
 
-int launch_score_rows(const float* emb, int64_t nd, const int32_t* rows, int64_t n_rows, int64_t q_offset,
-                      SgemvSplit sp, float* S, hipStream_t st) {
+int launch_topk_large(const float* emb, int64_t nd, const int32_t* active, const int32_t* n_active, int64_t max_q,
+                      int64_t q_offset, int K, int32_t* cand, float* S, SgemvSplit sp, int32_t* ties, hipStream_t st) {
+  return launch_topk_large_dim(emb, nd, 16, active, n_active, max_q, q_offset, K, cand, S, sp, ties, st);
+}
+
+int launch_score_rows_dim(const float* emb, int64_t nd, int dim, const int32_t* rows, int64_t n_rows, int64_t q_offset,
+                          SgemvSplit sp, float* S, hipStream_t st) {
   for (int64_t r0 = 0; r0 < n_rows; r0 += 4096) {
     const int m = (int)std::min<int64_t>(4096, n_rows - r0);
-    k_score_rows<<<cdiv(nd, kScoreThreads), kScoreThreads, 0, st>>>(emb, nd, rows + r0, m, q_offset, sp,
-                                                                     S + r0 * nd);
+    if (dim == 32)
+      k_score_rows<32><<<cdiv(nd, kScoreThreads), kScoreThreads, 0, st>>>(emb, nd, rows + r0, m, q_offset, sp,
+                                                                           S + r0 * nd);
+    else
+      k_score_rows<16><<<cdiv(nd, kScoreThreads), kScoreThreads, 0, st>>>(emb, nd, rows + r0, m, q_offset, sp,
+                                                                           S + r0 * nd);
   }
   FWAV_LAUNCH_CHECK("fwav_score_rows");
   return FWAV_OK;
+}
+
+int launch_score_rows(const float* emb, int64_t nd, const int32_t* rows, int64_t n_rows, int64_t q_offset,
+                      SgemvSplit sp, float* S, hipStream_t st) {
+  return launch_score_rows_dim(emb, nd, 16, rows, n_rows, q_offset, sp, S, st);
 }
 
 }  // namespace fwav

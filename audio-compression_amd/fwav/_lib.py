@@ -56,6 +56,17 @@ SIGNATURES = {
     "fwav_tie_rows_out": (I32, [P, I64, P, P, P, P, P, P, P, P, P, P, P]),
     "fwav_tie_list_size": (I64, [I64]),
     "fwav_emb16_from_emb": (I32, [P, I64, P, P]),
+    "fwav_embh_elems": (SZ, [I64, I32]),
+    "fwav_embh_from_emb": (I32, [P, I64, I32, P, P]),
+    "fwav_embed_tables_dim_size": (SZ, [I32, I32]),
+    "fwav_embed_tables_dim": (I32, [I32, I32, P]),
+    "fwav_pool_embed_dim": (I32, [P, I64, I32, I32, I32, I32, P, P, P, P, P, SZ, P]),
+    "fwav_prune_dim": (I32, [P, I64, I64, I32, F32, I32, P, I64, I32, I32, P, P, P, P, P]),
+    "fwav_sim_topk_dim_workspace_size": (SZ, [I64, I64, I32, I32]),
+    "fwav_sim_topk_dim": (I32, [P, P, I64, I32, P, P, I64, I64, I32, I32, P, P, P, SZ, P]),
+    "fwav_score_rows_dim": (I32, [P, I64, I32, P, I64, I64, I32, P, P]),
+    "fwav_tie_check_dim": (I32, [P, I64, I32, P, I32, P, I64, P, I32, I64, I32, P, I64, I32, P, P]),
+    "fwav_debug_score_dim": (I32, [P, P, I32, I32, P]),
     "fwav_decode_workspace_size": (SZ, [I64, I32, I32]),
     "fwav_decode": (I32, [P, P, P, P, I64, I32, P, I64, I32, F64, F32, F64, P, P, P, P, P, SZ, P]),
     "fwav_decode_span": (I32, []),

@@ -50,9 +50,9 @@ def compress_audio(signal, framerate, sampwidth, tile_size=1024, emb_dim=16, top
     """fractal.py:1045 — returns ``(matches, domains, n_ranges, range_size, tile_size, domain_step,
     energy_thresh, original_len)``.  ``embedding`` as :func:`fwav.engine.compress_device`: "pocketfft" embeds with
     scipy's own DCT sequence at every supported range size (ValueError at the others), so that tiles of 4352 samples
-    and more give the reference's matches too."""
-    if emb_dim != 16:
-        raise NotImplementedError("the MI355X engine implements the reference's default emb_dim=16 only")
+    and more give the reference's matches too.  ``emb_dim``: 16 (default) or 32, the reference's rows of two heads
+    of 16 coefficients (with embedding="matrix"; "pocketfft" is ValueError there); NotImplementedError otherwise."""
+    engine.check_emb_dim(emb_dim, embedding)  # 16 or 32; NotImplementedError for any other width
     k = _default_k() if top_k is None else int(top_k)
     dev = engine.require_device(device)
     sig = np.asarray(signal, dtype=np.float32)
@@ -60,7 +60,7 @@ def compress_audio(signal, framerate, sampwidth, tile_size=1024, emb_dim=16, top
     t = torch.from_numpy(np.ascontiguousarray(sig)).to(dev)
     copy = _PoolCopy(dev)
     res = engine.compress_device(t, tile_size, k, energy_thresh=energy_thresh, fast_mode=fast_mode,
-                                 on_pool=copy.start, embedding=embedding)
+                                 on_pool=copy.start, embedding=embedding, emb_dim=emb_dim)
     return device_result_to_tuple(res, copy)
 
 
@@ -155,9 +155,10 @@ def compute_snr(original, reconstructed):
     return 10.0 * np.log10(signal_power / noise_power)
 
 
-def process_file_compress(path, outdir=None, tile=1024, energy_thresh=1e-4, use_gpu=False, embedding="matrix"):
-    """fractal.py:1491-1521 (the positional CLI OUTPUT is used as a directory, quirk Q8).  ``embedding`` as
-    :func:`compress_audio`."""
+def process_file_compress(path, outdir=None, tile=1024, energy_thresh=1e-4, use_gpu=False, embedding="matrix",
+                          emb_dim=16):
+    """fractal.py:1491-1521 (the positional CLI OUTPUT is used as a directory, quirk Q8).  ``embedding`` and
+    ``emb_dim`` as :func:`compress_audio`."""
     try:
         start = time.time()
         signal, framerate, sampwidth = read_wav_mono(path)
@@ -165,7 +166,7 @@ def process_file_compress(path, outdir=None, tile=1024, energy_thresh=1e-4, use_
             signal = np.clip(signal.astype(np.float32), -1.0, 1.0)
         matches, domains, n_ranges, range_size, tile_size, domain_step, energy_threshold, original_len = \
             compress_audio(signal, framerate, sampwidth, tile_size=tile, energy_thresh=energy_thresh, use_gpu=use_gpu,
-                           embedding=embedding)
+                           embedding=embedding, emb_dim=emb_dim)
         logger.info(f"Processed {len(matches)} ranges, domain matrix shape {domains.shape}")
         if outdir and not os.path.exists(outdir):
             os.makedirs(outdir)

@@ -1,10 +1,11 @@
 """Command line, same sub-commands / flags / output naming as the reference (fractal.py:1550-1669).
 
   python fractal.py compress IN OUT [--tile 1024] [--energy-thresh 1e-4] [--gpu] [--batch] [--out DIR] [--workers 4]
-                            [--embedding {matrix,pocketfft}]
+                            [--embedding {matrix,pocketfft}] [--emb-dim {16,32}]
   python fractal.py decompress IN [--out PATH] [--iter 8] [--eps 1e-3] [--gpu] [--batch] [--workers 4]
 
---embedding is this port's one extra flag: "pocketfft" embeds with scipy's own DCT sequence at every supported range
+--embedding and --emb-dim are this port's extra flags.  --emb-dim is compress_audio's emb_dim (the reference's CLI
+never passes it): 32 embeds with two heads of 16 coefficients.  --embedding "pocketfft" embeds with scipy's own DCT sequence at every supported range
 size (tiles of 4352 samples and more then give the reference's file too); the default "matrix" is bit-exact at range
 sizes 4, 8 and 16.  Non-batch OUTPUT / --out are used as directories (quirk Q8, fractal.py:1509, 1538).  Batch mode skips
 files whose output exists and writes compression_metrics.json / decompression_metrics.json.  The reference's
@@ -80,6 +81,8 @@ def main(argv=None):
     pc.add_argument("--embedding", choices=("matrix", "pocketfft"), default="matrix",
                     help="domain embedding: the matrix DCT (bit-exact at range sizes 4, 8, 16) or scipy's pocketfft "
                          "sequence (bit-exact at every supported range size; an unsupported one is an error)")
+    pc.add_argument("--emb-dim", type=int, choices=(16, 32), default=16,
+                    help="embedding width (compress_audio's emb_dim): two heads of 8 or of 16 DCT coefficients")
     pd = sub.add_parser("decompress")
     pd.add_argument("input", help="input file or directory")
     pd.add_argument("--out", default=None, help="output file or directory")
@@ -94,7 +97,8 @@ def main(argv=None):
         if not args.batch:
             if args.output is None:
                 parser.error("compress requires OUTPUT unless --batch is used")
-            return _compress_job((args.input, args.output, args.tile, args.energy_thresh, args.gpu, args.embedding))
+            return _compress_job((args.input, args.output, args.tile, args.energy_thresh, args.gpu, args.embedding,
+                                  args.emb_dim))
         if args.output is not None:
             parser.error("Do not provide positional OUTPUT when using --batch; use --out instead")
         out_dir = args.out or args.input
@@ -105,7 +109,8 @@ def main(argv=None):
             logger.info("No files to compress — all already exist.")
             return None
         results = _run_pool(_compress_job, [(f, os.path.join(out_dir, os.path.basename(f) + ".fwav"), args.tile,
-                                             args.energy_thresh, args.gpu, args.embedding) for f in todo],
+                                             args.energy_thresh, args.gpu, args.embedding, args.emb_dim)
+                                            for f in todo],
                             args.workers)
         metrics_file = os.path.join(out_dir, "compression_metrics.json")
         os.makedirs(os.path.dirname(metrics_file) or ".", exist_ok=True)

@@ -10,6 +10,7 @@ Reference map (``/root/reference/fractal.py``):
   build_domains_memmap :285-334 + build_domain_embeddings :238-280 → fwav_pool_embed
   cpu_worker energy prune :601-603, pad :622               → fwav_prune
   linear top-K :535-541, 617-620                           → fwav_sim_topk (+ fwav_tie_check / fwav.ties for exact ties)
+  the same stages on rows of emb_dim = 32 columns (:275)   → fwav_pool_embed_dim, fwav_prune_dim, fwav_sim_topk_dim, …
   _process_gpu_batch :757-850                              → fwav_affine
   decompress_audio :1378-1473                              → fwav_decode
 """
@@ -73,15 +74,62 @@ def check_embedding(embedding: str, rs: int) -> str:
     return embedding
 
 
-def embed_tables(rs: int, device: torch.device, embedding: str = "matrix") -> torch.Tensor:
+#: the embedding widths the engine implements (compress_audio's emb_dim): 16, the reference's default, through the
+#: entry points above; 32 through the *_dim entry points of include/fwav.h
+EMB_DIMS = (16, 32)
+
+
+def check_emb_dim(emb_dim, embedding: str = "matrix") -> int:
+    """``emb_dim`` validated: NotImplementedError for a width other than 16 and 32, ValueError for 32 together with
+    embedding="pocketfft" (the exact plans are built for heads of 8 coefficients)."""
+    if emb_dim not in EMB_DIMS:
+        raise NotImplementedError(f"emb_dim={emb_dim!r}: the MI355X engine supports emb_dim 16 and 32")
+    if emb_dim != 16 and embedding == "pocketfft":
+        raise ValueError("embedding='pocketfft' with emb_dim=32 is out of scope: use embedding='matrix'")
+    return int(emb_dim)
+
+
+def embed_tables(rs: int, device: torch.device, embedding: str = "matrix", emb_dim: int = 16) -> torch.Tensor:
     check_embedding(embedding, rs)
-    key = (rs, str(device), embedding)
+    dim = check_emb_dim(emb_dim, embedding)
+    key = (rs, dim, str(device), embedding)
     if key not in _TABLES:
-        size_fn, fill_fn, _ = EMBEDDINGS[embedding]
-        host = np.zeros(size_call(size_fn, rs), np.float64)
-        call(fill_fn, rs, host.ctypes.data)
+        if dim == 16:
+            size_fn, fill_fn, _ = EMBEDDINGS[embedding]
+            host = np.zeros(size_call(size_fn, rs), np.float64)
+            call(fill_fn, rs, host.ctypes.data)
+        else:
+            host = np.zeros(size_call("fwav_embed_tables_dim_size", rs, dim), np.float64)
+            call("fwav_embed_tables_dim", rs, dim, host.ctypes.data)
         _TABLES[key] = torch.from_numpy(host).to(device)
     return _TABLES[key]
+
+
+def _topk_ws_size(dim: int, mq: int, nd: int, k: int, f16: bool) -> int:
+    """Bytes of the search's workspace for mq queries (fwav_sim_topk / fwav_sim_topk_dim)."""
+    if dim != 16:
+        return size_call("fwav_sim_topk_dim_workspace_size", mq, nd, dim, k)
+    return size_call("fwav_sim_topk_workspace_size", mq, nd, k) if (f16 or k > 64) else 0
+
+
+def _sim_topk(dim, emb, emb16, nd, active_ptr, n_active_ptr, mq, lo, k, threads, cand, ties, wsk, wk, st) -> None:
+    """fwav_sim_topk, or fwav_sim_topk_dim on rows of ``dim`` != 16 columns (emb16 then its fp16 table)."""
+    if dim == 16:
+        call("fwav_sim_topk", emb.data_ptr(), _p(emb16), nd, active_ptr, n_active_ptr, mq, lo, k, threads,
+             cand.data_ptr(), _p(ties), wsk.data_ptr(), wk, st)
+    else:
+        call("fwav_sim_topk_dim", emb.data_ptr(), _p(emb16), nd, dim, active_ptr, n_active_ptr, mq, lo, k, threads,
+             cand.data_ptr(), _p(ties), wsk.data_ptr(), wk, st)
+
+
+def _tie_check(dim, rsh, m, rs, cand, k, pool, nd, emb, lo, threads, ties, max_ties, mode, resolve, st) -> None:
+    """fwav_tie_check, or fwav_tie_check_dim on rows of ``dim`` != 16 columns."""
+    if dim == 16:
+        call("fwav_tie_check", rsh.data_ptr(), m, rs, cand.data_ptr(), k, pool.data_ptr(), nd, emb.data_ptr(), lo,
+             threads, ties.data_ptr(), max_ties, mode, resolve.data_ptr(), st)
+    else:
+        call("fwav_tie_check_dim", rsh.data_ptr(), m, rs, cand.data_ptr(), k, pool.data_ptr(), nd, emb.data_ptr(), dim,
+             lo, threads, ties.data_ptr(), max_ties, mode, resolve.data_ptr(), st)
 
 
 _ZERO_CAND_DEV: dict = {}
@@ -206,7 +254,8 @@ def _compress_device(sig: torch.Tensor, tile_size: int, top_k: int, energy_thres
                      keep_intermediates: bool = False, events: Optional[dict] = None,
                      search: str = "f16", on_pool=None, blas_threads: Optional[int] = None,
                      tie_order: str = "numpy", defer_ties: bool = False,
-                     sub_blocks: Optional[int] = None, embedding: str = "matrix") -> DeviceCompressed:
+                     sub_blocks: Optional[int] = None, embedding: str = "matrix",
+                     emb_dim: int = 16) -> DeviceCompressed:
     """Run the compress hot path on ``sig`` (1-D float32 tensor on a HIP device).
 
     ``shard=(lo, hi)`` restricts candidate search and the affine solve to ranges ``[lo, hi)`` (the
@@ -232,6 +281,10 @@ def _compress_device(sig: torch.Tensor, tile_size: int, top_k: int, energy_thres
     matrix DCT elsewhere; ``"pocketfft"`` runs scipy's own pocketfft sequence at every supported range size (4 to 49
     and 50, 54, 56, 60, 63, 64: tiles up to 12,799 and a few above), so the embedding, and with it every candidate set
     and match, is the reference's bit for bit there too; ValueError at any other range size.
+    ``emb_dim=32`` builds the reference's wide rows (two heads of 16 coefficients, ``res.emb`` f32[nd·32]) and searches
+    them through the ``*_dim`` entry points (K ≤ 64: fp16 pre-filter + exact rescoring, fwav_topk_wide.hip); every
+    option above works on top, except ``embedding="pocketfft"`` (ValueError) and ``search="f32"`` (ValueError: the
+    wide search has one kernel); any other width is NotImplementedError.
     """
     if sig.dim() != 1 or sig.dtype != torch.float32 or not sig.is_cuda:
         raise ValueError("compress_device expects a 1-D float32 device tensor")
@@ -252,6 +305,7 @@ def _compress_device(sig: torch.Tensor, tile_size: int, top_k: int, energy_thres
     if k > size_call("fwav_topk_max_k"):
         raise ValueError(f"top_k={k} > {size_call('fwav_topk_max_k')} is not supported by the HIP search")
     check_embedding(embedding, rs)
+    dim = check_emb_dim(emb_dim, embedding)
     if tie_order not in TIE_MODES:
         raise ValueError("tie_order must be 'numpy' (the reference's order of exactly tied scores wherever it decides a"
                          " match), 'numpy_sets' (and wherever it decides a candidate set), 'numpy_rows' (and wherever it"
@@ -271,17 +325,27 @@ def _compress_device(sig: torch.Tensor, tile_size: int, top_k: int, energy_thres
         if res.is_silent() or n < tile_size:
             return _empty(n, rs, tile_size, step, energy_thresh, k)
         raise ValueError("mmap length is greater than file size")  # quirk Q9 (fractal.py:1190-1195)
-    tab = embed_tables(rs, dev, embedding)
+    tab = embed_tables(rs, dev, embedding, dim)
     pool = torch.empty(nd * rs, dtype=torch.float32, device=dev)
-    emb = torch.empty(nd * 16, dtype=torch.float32, device=dev)
+    emb = torch.empty(nd * dim, dtype=torch.float32, device=dev)
     if search not in ("f16", "f32"):
         raise ValueError("search must be 'f16' (fp16 pre-filter + exact f32 rescoring) or 'f32'")
-    emb16 = torch.empty(2 * ((nd + 255) // 256) * 256 * 16, dtype=torch.float16, device=dev) if search == "f16" else None
+    if dim != 16 and search != "f16":
+        raise ValueError("search='f32' is not available with emb_dim=32 (the wide search has one kernel)")
+    if dim != 16:
+        emb16 = torch.empty(size_call("fwav_embh_elems", nd, dim), dtype=torch.float16, device=dev)
+    else:
+        emb16 = (torch.empty(2 * ((nd + 255) // 256) * 256 * 16, dtype=torch.float16, device=dev)
+                 if search == "f16" else None)
     ws_p = size_call("fwav_pool_workspace_size", n, tile_size, rs, step)
     wsp = torch.empty(max(ws_p, 16), dtype=torch.uint8, device=dev)
     _mark(events, "pool_embed")
-    call(EMBEDDINGS[embedding][2], sig.data_ptr(), n, tile_size, rs, step, tab.data_ptr(), pool.data_ptr(),
-         emb.data_ptr(), _p(emb16), wsp.data_ptr(), ws_p, st)
+    if dim != 16:
+        call("fwav_pool_embed_dim", sig.data_ptr(), n, tile_size, rs, step, dim, tab.data_ptr(), pool.data_ptr(),
+             emb.data_ptr(), _p(emb16), wsp.data_ptr(), ws_p, st)
+    else:
+        call(EMBEDDINGS[embedding][2], sig.data_ptr(), n, tile_size, rs, step, tab.data_ptr(), pool.data_ptr(),
+             emb.data_ptr(), _p(emb16), wsp.data_ptr(), ws_p, st)
     _mark(events, "pool_embed")
     if on_pool is not None:
         on_pool(pool)
@@ -306,8 +370,12 @@ def _compress_device(sig: torch.Tensor, tile_size: int, top_k: int, energy_thres
     if m > 0:
         _mark(events, "prune")
         zc = _zero_cand_device(nd, k, dev)
-        call("fwav_prune", rsh.data_ptr(), m, lo, rs, float(F32(energy_thresh * 0.75)), int(bool(fast_mode)),
-             emb.data_ptr(), nd, k, zc.data_ptr(), cand.data_ptr(), active.data_ptr(), n_active.data_ptr(), st)
+        if dim != 16:
+            call("fwav_prune_dim", rsh.data_ptr(), m, lo, rs, float(F32(energy_thresh * 0.75)), int(bool(fast_mode)),
+                 emb.data_ptr(), nd, dim, k, zc.data_ptr(), cand.data_ptr(), active.data_ptr(), n_active.data_ptr(), st)
+        else:
+            call("fwav_prune", rsh.data_ptr(), m, lo, rs, float(F32(energy_thresh * 0.75)), int(bool(fast_mode)),
+                 emb.data_ptr(), nd, k, zc.data_ptr(), cand.data_ptr(), active.data_ptr(), n_active.data_ptr(), st)
         _mark(events, "prune")
         sc = float(abs(F32(s_clip)))
         nsub = 1
@@ -324,12 +392,12 @@ def _compress_device(sig: torch.Tensor, tile_size: int, top_k: int, energy_thres
             sliced = nsub > 1 or (defer_ties and nd >= SUB_BLOCK_MIN_DOMAINS)
         if not sliced:
             _mark(events, "sim_topk")
-            wk = size_call("fwav_sim_topk_workspace_size", m, nd, k) if (emb16 is not None or k > 64) else 0
+            wk = _topk_ws_size(dim, m, nd, k, emb16 is not None)
             wsk = torch.empty(max(wk, 16), dtype=torch.uint8, device=dev)
             ties = (torch.empty(size_call("fwav_tie_list_size", m), dtype=torch.int32, device=dev)
                     if tie_order != "index" else None)
-            call("fwav_sim_topk", emb.data_ptr(), _p(emb16), nd, active.data_ptr(), n_active.data_ptr(), m, lo, k,
-                 threads, cand.data_ptr(), _p(ties), wsk.data_ptr(), wk, st)
+            _sim_topk(dim, emb, emb16, nd, active.data_ptr(), n_active.data_ptr(), m, lo, k, threads, cand, ties, wsk,
+                      wk, st)
             _mark(events, "sim_topk")
             _mark(events, "affine")
             call("fwav_affine", rsh.data_ptr(), m, rs, cand.data_ptr(), k, pool.data_ptr(), nd, sc, idx.data_ptr(),
@@ -339,15 +407,14 @@ def _compress_device(sig: torch.Tensor, tile_size: int, top_k: int, energy_thres
             # exactly tied scores whose order can change a match: numpy's own ranking for those rows (fwav.ties)
             _mark(events, "ties")
             resolve = torch.empty(m + 1, dtype=torch.int32, device=dev)
-            call("fwav_tie_check", rsh.data_ptr(), m, rs, cand.data_ptr(), k, pool.data_ptr(), nd, emb.data_ptr(), lo,
-                 threads, ties.data_ptr(), m, TIE_MODES[tie_order], resolve.data_ptr(), st)
+            _tie_check(dim, rsh, m, rs, cand, k, pool, nd, emb, lo, threads, ties, m, TIE_MODES[tie_order], resolve, st)
 
             def finish(stream_id):
                 counts = torch.stack([ties[0], resolve[0]]).cpu()
                 res.n_ties, res.n_resolved = int(counts[0]), int(counts[1])
                 if res.n_resolved:
                     _ties.resolve_rows(resolve[1:1 + res.n_resolved], emb=emb, n_domains=nd, q_offset=lo, k=k,
-                                       threads=threads, ranges=rsh, range_size=rs, pool=pool, s_clip=sc, cand=cand,
+                                       threads=threads, emb_dim=dim, ranges=rsh, range_size=rs, pool=pool, s_clip=sc, cand=cand,
                                        outs=(idx, s, o, sym, err), stream=stream_id)
 
             def stage(stream_id):
@@ -359,7 +426,7 @@ def _compress_device(sig: torch.Tensor, tile_size: int, top_k: int, energy_thres
                     return None
                 rows = resolve[1:1 + res.n_resolved]
                 futs = _ties.rank_rows(_ties.score_row_launches(rows, emb=emb, n_domains=nd, q_offset=lo,
-                                                                threads=threads, stream=stream_id),
+                                                                threads=threads, stream=stream_id, emb_dim=dim),
                                        res.n_resolved, nd, k)
                 return rows, futs
 
@@ -377,7 +444,8 @@ def _compress_device(sig: torch.Tensor, tile_size: int, top_k: int, energy_thres
             _mark(events, "ties")
         elif sliced:
             ties = _search_sub_blocks(nsub, m, nd, k, lo, rs, threads, sc, tie_order, emb, emb16, active, n_active,
-                                      rsh, pool, cand, (idx, s, o, sym, err), res, events, st, defer=defer_ties)
+                                      rsh, pool, cand, (idx, s, o, sym, err), res, events, st, defer=defer_ties,
+                                      dim=dim)
     res.pool, res.idx, res.s, res.o, res.sym, res.err, res.n_active = pool, idx, s, o, sym, err, n_active
     if keep_intermediates:
         res.ranges, res.emb, res.cand, res.active = ranges, emb, cand, active
@@ -423,7 +491,7 @@ class _Staged:
 
 
 def _search_sub_blocks(nsub, m, nd, k, lo, rs, threads, sc, tie_order, emb, emb16, active, n_active, rsh, pool, cand,
-                       outs, res, events, st, defer=False):
+                       outs, res, events, st, defer=False, dim=16):
     """The search as ``nsub`` launches over consecutive slices of the active list.  After each slice's search and tie
     check the host reads its tie counts (one synchronisation), queues the exact score rows of its tied rows and hands
     their copies and numpy's ranking to the driver thread (fwav.ties.rank_rows_async); then the next slice searches.
@@ -431,8 +499,7 @@ def _search_sub_blocks(nsub, m, nd, k, lo, rs, threads, sc, tie_order, emb, emb1
     slices' tie records as one list."""
     dev = rsh.device
     bounds = _slice_bounds(m, nsub)
-    wk = max(size_call("fwav_sim_topk_workspace_size", b - a, nd, k) for a, b in bounds) \
-        if (emb16 is not None or k > 64) else 0
+    wk = max(_topk_ws_size(dim, b - a, nd, k, emb16 is not None) for a, b in bounds)
     wsk = torch.empty(max(wk, 16), dtype=torch.uint8, device=dev)
     pend = []
     lists = []  # each slice's tie records
@@ -442,11 +509,9 @@ def _search_sub_blocks(nsub, m, nd, k, lo, rs, threads, sc, tie_order, emb, emb1
         mq = j1 - j0
         na = torch.clamp(n_active - j0, 0, mq).to(torch.int32)
         ties = torch.empty(size_call("fwav_tie_list_size", mq), dtype=torch.int32, device=dev)
-        call("fwav_sim_topk", emb.data_ptr(), _p(emb16), nd, active[j0:].data_ptr(), na.data_ptr(), mq, lo, k, threads,
-             cand.data_ptr(), ties.data_ptr(), wsk.data_ptr(), wk, st)
+        _sim_topk(dim, emb, emb16, nd, active[j0:].data_ptr(), na.data_ptr(), mq, lo, k, threads, cand, ties, wsk, wk, st)
         resolve = torch.empty(mq + 1, dtype=torch.int32, device=dev)
-        call("fwav_tie_check", rsh.data_ptr(), m, rs, cand.data_ptr(), k, pool.data_ptr(), nd, emb.data_ptr(), lo,
-             threads, ties.data_ptr(), mq, TIE_MODES[tie_order], resolve.data_ptr(), st)
+        _tie_check(dim, rsh, m, rs, cand, k, pool, nd, emb, lo, threads, ties, mq, TIE_MODES[tie_order], resolve, st)
         counts = torch.stack([ties[0], resolve[0]]).cpu()
         if _ties._TRACE:
             import time
@@ -459,7 +524,7 @@ def _search_sub_blocks(nsub, m, nd, k, lo, rs, threads, sc, tie_order, emb, emb1
         if nr_j:
             rows = resolve[1:1 + nr_j]
             pend.append((rows, _ties.rank_rows_async(rows, emb=emb, n_domains=nd, q_offset=lo, k=k, threads=threads,
-                                                     stream=st)))
+                                                     stream=st, emb_dim=dim)))
     _mark(events, "sim_topk")
     _mark(events, "affine")
     call("fwav_affine", rsh.data_ptr(), m, rs, cand.data_ptr(), k, pool.data_ptr(), nd, sc, *[t.data_ptr() for t in outs],

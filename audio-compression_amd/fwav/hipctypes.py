@@ -164,7 +164,7 @@ def _i32(buf: DeviceBuffer, count: int) -> np.ndarray:
 
 def compress(signal: np.ndarray, tile_size: int, top_k: int, energy_thresh: float = 1e-4, fast_mode: bool = True,
              s_clip: float = 16.0, tie_order: str = "numpy", threads: int | None = None,
-             embedding: str = "matrix") -> dict | None:
+             embedding: str = "matrix", emb_dim: int = 16) -> dict | None:
     """compress_audio's device pipeline (fractal.py:1040-1256) with HIP buffers only, on the null stream:
 
       fwav_voiced_ranges → fwav_weighted_energy (silent test, :1083) → fwav_pool_embed → fwav_prune → fwav_sim_topk
@@ -173,10 +173,18 @@ def compress(signal: np.ndarray, tile_size: int, top_k: int, energy_thresh: floa
 
     Returns None where the reference returns its empty tuple (input shorter than a tile, or silent), raises the
     reference's ValueErrors (empty input; more ranges than domains, quirk Q9), else a dict of host arrays: idx, s, o,
-    sym, err (the match tuples), pool f32[nd, rs], emb f32[nd, 16], cand i32[nr, K], n_ranges, range_size,
+    sym, err (the match tuples), pool f32[nd, rs], emb f32[nd, emb_dim], cand i32[nr, K], n_ranges, range_size,
     domain_step, n_domains, n_ties, n_resolved.  ``tie_order`` as fwav.engine.compress_device ("numpy",
     "numpy_sets", "numpy_rows" or "index"), ``embedding`` too: "matrix" (fwav_pool_embed) or "pocketfft"
-    (fwav_pool_embed_exact: scipy's DCT sequence at every supported range size, ValueError at the others)."""
+    (fwav_pool_embed_exact: scipy's DCT sequence at every supported range size, ValueError at the others).
+    ``emb_dim=32`` runs the same sequence through the ``*_dim`` entry points (fwav_pool_embed_dim, fwav_prune_dim,
+    fwav_sim_topk_dim, fwav_tie_check_dim, fwav_score_rows_dim) on rows of 32 columns (emb f32[nd, 32]); it needs
+    embedding="matrix" (ValueError otherwise), and any width but 16 and 32 is NotImplementedError."""
+    if emb_dim not in (16, 32):
+        raise NotImplementedError(f"emb_dim={emb_dim!r}: the MI355X engine supports emb_dim 16 and 32")
+    if emb_dim != 16 and embedding == "pocketfft":
+        raise ValueError("embedding='pocketfft' with emb_dim=32 is out of scope: use embedding='matrix'")
+    dim, wide = int(emb_dim), emb_dim != 16
     modes = {"numpy": 0, "numpy_sets": 1, "numpy_rows": 2, "index": -1}  # → fwav_tie_check's exact_sets
     if tie_order not in modes:
         raise ValueError("tie_order must be 'numpy', 'numpy_sets', 'numpy_rows' or 'index'")
@@ -186,7 +194,11 @@ def compress(signal: np.ndarray, tile_size: int, top_k: int, energy_thresh: floa
         raise ValueError("a cannot be empty")  # np.convolve on zero frames (fractal.py:895)
     k = int(top_k)
     rs, step = geometry(tile_size)
-    tab = _embed_tables(rs, embedding)
+    if wide:
+        tab = np.empty(size_call("fwav_embed_tables_dim_size", rs, dim), np.float64)
+        call("fwav_embed_tables_dim", rs, dim, tab.ctypes.data)
+    else:
+        tab = _embed_tables(rs, embedding)
     frame = 2 * rs
     nr = -(-n // rs)
     nd = 0 if n < tile_size else (n - tile_size) // step + 1
@@ -209,29 +221,45 @@ def compress(signal: np.ndarray, tile_size: int, top_k: int, energy_thresh: floa
     if silent:
         return None
     d_tab = DeviceBuffer.from_array(tab)
-    d_pool, d_emb = DeviceBuffer(4 * nd * rs), DeviceBuffer(4 * nd * 16)
-    d_emb16 = DeviceBuffer(2 * size_call("fwav_emb16_elems", nd))
+    d_pool, d_emb = DeviceBuffer(4 * nd * rs), DeviceBuffer(4 * nd * dim)
+    d_emb16 = DeviceBuffer(2 * (size_call("fwav_embh_elems", nd, dim) if wide else size_call("fwav_emb16_elems", nd)))
     wsp = size_call("fwav_pool_workspace_size", n, tile_size, rs, step)
     d_wsp = DeviceBuffer(wsp)
-    call(EMBEDDINGS[embedding][2], d_sig.value, n, tile_size, rs, step, d_tab.value, d_pool.value, d_emb.value,
-         d_emb16.value, d_wsp.value, wsp, None)
+    if wide:
+        call("fwav_pool_embed_dim", d_sig.value, n, tile_size, rs, step, dim, d_tab.value, d_pool.value, d_emb.value,
+             d_emb16.value, d_wsp.value, wsp, None)
+    else:
+        call(EMBEDDINGS[embedding][2], d_sig.value, n, tile_size, rs, step, d_tab.value, d_pool.value, d_emb.value,
+             d_emb16.value, d_wsp.value, wsp, None)
     d_cand, d_active, d_nact = DeviceBuffer(4 * nr * k), DeviceBuffer(4 * nr), DeviceBuffer(4)
     d_zc = DeviceBuffer.from_array(zero_query_candidates(nd, k))
-    call("fwav_prune", d_ranges.value, nr, 0, rs, float(np.float32(energy_thresh * 0.75)), int(bool(fast_mode)),
-         d_emb.value, nd, k, d_zc.value, d_cand.value, d_active.value, d_nact.value, None)
-    wsk = size_call("fwav_sim_topk_workspace_size", nr, nd, k)
-    d_wsk = DeviceBuffer(wsk)
     d_ties = DeviceBuffer(4 * size_call("fwav_tie_list_size", nr))
-    call("fwav_sim_topk", d_emb.value, d_emb16.value, nd, d_active.value, d_nact.value, nr, 0, k, T, d_cand.value,
-         d_ties.value, d_wsk.value, wsk, None)
+    if wide:
+        call("fwav_prune_dim", d_ranges.value, nr, 0, rs, float(np.float32(energy_thresh * 0.75)),
+             int(bool(fast_mode)), d_emb.value, nd, dim, k, d_zc.value, d_cand.value, d_active.value, d_nact.value, None)
+        wsk = size_call("fwav_sim_topk_dim_workspace_size", nr, nd, dim, k)
+        d_wsk = DeviceBuffer(wsk)
+        call("fwav_sim_topk_dim", d_emb.value, d_emb16.value, nd, dim, d_active.value, d_nact.value, nr, 0, k, T,
+             d_cand.value, d_ties.value, d_wsk.value, wsk, None)
+    else:
+        call("fwav_prune", d_ranges.value, nr, 0, rs, float(np.float32(energy_thresh * 0.75)), int(bool(fast_mode)),
+             d_emb.value, nd, k, d_zc.value, d_cand.value, d_active.value, d_nact.value, None)
+        wsk = size_call("fwav_sim_topk_workspace_size", nr, nd, k)
+        d_wsk = DeviceBuffer(wsk)
+        call("fwav_sim_topk", d_emb.value, d_emb16.value, nd, d_active.value, d_nact.value, nr, 0, k, T, d_cand.value,
+             d_ties.value, d_wsk.value, wsk, None)
     outs = [DeviceBuffer(4 * nr), DeviceBuffer(4 * nr), DeviceBuffer(4 * nr), DeviceBuffer(nr), DeviceBuffer(4 * nr)]
     sc = float(abs(np.float32(s_clip)))
     call("fwav_affine", d_ranges.value, nr, rs, d_cand.value, k, d_pool.value, nd, sc, *[b.value for b in outs], None)
     n_ties = n_res = 0
     if tie_order != "index":
         d_res = DeviceBuffer(4 * (nr + 1))
-        call("fwav_tie_check", d_ranges.value, nr, rs, d_cand.value, k, d_pool.value, nd, d_emb.value, 0, T,
-             d_ties.value, nr, modes[tie_order], d_res.value, None)
+        if wide:
+            call("fwav_tie_check_dim", d_ranges.value, nr, rs, d_cand.value, k, d_pool.value, nd, d_emb.value, dim, 0,
+                 T, d_ties.value, nr, modes[tie_order], d_res.value, None)
+        else:
+            call("fwav_tie_check", d_ranges.value, nr, rs, d_cand.value, k, d_pool.value, nd, d_emb.value, 0, T,
+                 d_ties.value, nr, modes[tie_order], d_res.value, None)
         n_ties = int(_i32(d_ties, 1)[0])
         res = _i32(d_res, 1 + nr)
         n_res = int(res[0])
@@ -242,7 +270,10 @@ def compress(signal: np.ndarray, tile_size: int, top_k: int, energy_thresh: floa
             d_sr = DeviceBuffer(4 * nd)
             newc = np.empty((n_res, k), np.int32)
             for j in range(n_res):
-                call("fwav_score_rows", d_emb.value, nd, d_rows.value + 4 * j, 1, 0, T, d_sr.value, None)
+                if wide:
+                    call("fwav_score_rows_dim", d_emb.value, nd, dim, d_rows.value + 4 * j, 1, 0, T, d_sr.value, None)
+                else:
+                    call("fwav_score_rows", d_emb.value, nd, d_rows.value + 4 * j, 1, 0, T, d_sr.value, None)
                 newc[j] = numpy_topk_row(d_sr.to_array(np.float32, nd), k)
             d_newc = DeviceBuffer.from_array(newc)
             d_rsub = DeviceBuffer(4 * n_res * rs)
@@ -257,7 +288,7 @@ def compress(signal: np.ndarray, tile_size: int, top_k: int, energy_thresh: floa
     return dict(idx=_i32(outs[0], nr), s=outs[1].to_array(np.float32, nr), o=outs[2].to_array(np.float32, nr),
                 sym=outs[3].to_array(np.uint8, nr), err=outs[4].to_array(np.float32, nr),
                 pool=d_pool.to_array(np.float32, nd * rs).reshape(nd, rs),
-                emb=d_emb.to_array(np.float32, nd * 16).reshape(nd, 16), cand=_i32(d_cand, nr * k).reshape(nr, k),
+                emb=d_emb.to_array(np.float32, nd * dim).reshape(nd, dim), cand=_i32(d_cand, nr * k).reshape(nr, k),
                 n_ranges=nr, range_size=rs, domain_step=step, n_domains=nd, n_ties=n_ties, n_resolved=n_res)
 
 

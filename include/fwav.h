@@ -184,6 +184,50 @@ int fwav_tie_rows_out(const int32_t* rows, int64_t n, const int32_t* idx_in, con
  * sink: one float of device memory. */
 int fwav_debug_gather_rows(const float* table, int64_t n_rows, int rs, int64_t n, float* sink, void* stream);
 
+/* ------------------------------------------------------------------- emb_dim = 32 (wide embeddings)
+ * compress_audio(emb_dim=32): the reference builds each embedding row from two heads of emb_dim / 2 coefficients
+ * (fractal.py:275, 166-208, 154-164), so a row is [tonal: min(16, range_size − 1) values, zero-padded to 16]
+ * [transient: min(16, range_size) values][zeros to 32].  The entry points below are the emb_dim = 16 ones above with
+ * rows of `emb_dim` floats; each accepts emb_dim = 32 only (FWAV_ERR_ARG otherwise, before any device work) and keeps
+ * the contract of the entry point it is named after.
+ *   fwav_pool_embed_dim: pool as fwav_pool_embed; emb f32[n_domains·32], bit-exact at range sizes 4, 8 and 16 (the
+ *     same DCT code, numpy's sdot order for the 16-value tonal norm, and for a transient head of 16 values OpenBLAS's
+ *     ddot order: four lanes l[i % 4] += x_i², folded (l0 + l2) + (l1 + l3)), the f64 matrix DCT with fwav_pool_embed's
+ *     accuracy elsewhere.  tab = device copy of fwav_embed_tables_dim(range_size, 32) (fwav_embed_tables_dim_size
+ *     doubles).  embh (optional) = the fp16 table of fwav_sim_topk_dim, f16[fwav_embh_elems(n_domains, 32)]: f16(emb)
+ *     tiled [chunk of 256 domains][column group of 8][256][8], rows past n_domains zero; fwav_embh_from_emb writes
+ *     it from embedding rows that came from elsewhere (tests).
+ *   fwav_prune_dim: the all-zero query test runs over 32 columns.
+ *   fwav_sim_topk_dim: scores in OpenBLAS's sgemv order for rows of 32 columns (one thread while 32·n_domains <
+ *     460,800; fwav_common.h sgemv_dim).  K ≤ 64: an fp16 MFMA pre-filter with a proven error bound in front of exact
+ *     f32 rescoring (fwav_topk_wide.hip; needs embh, no workspace); K > 64: fwav_topk_large.hip's select on 32-wide
+ *     score rows (embh unused, workspace of fwav_sim_topk_dim_workspace_size bytes).  *n_active is read on the device.
+ *   fwav_score_rows_dim, fwav_tie_check_dim: the tie resolution's two device steps on 32-wide rows.
+ *   fwav_debug_score_dim (host, no device; tests): out[0] = one pair's exact score through the search's own helper
+ *     (sgemv kernel `kind` 0, 1 or 2), out[1] = its fp16 pre-filter score (f32 sum in index order), out[2] = δ, the
+ *     bound on their difference that the pre-filter relies on. */
+size_t fwav_embh_elems(int64_t n_domains, int emb_dim);
+int fwav_embh_from_emb(const float* emb, int64_t n_domains, int emb_dim, void* embh, void* stream);
+size_t fwav_embed_tables_dim_size(int range_size, int emb_dim);
+int fwav_embed_tables_dim(int range_size, int emb_dim, double* tab_host);
+int fwav_pool_embed_dim(const float* sig, int64_t n, int tile, int range_size, int step, int emb_dim,
+                        const double* tab, float* pool, float* emb, void* embh, void* workspace, size_t ws_bytes,
+                        void* stream);
+int fwav_prune_dim(const float* ranges, int64_t n, int64_t q_offset, int range_size, float prune_thr, int fast_mode,
+                   const float* emb, int64_t n_domains, int emb_dim, int k, const int32_t* zero_cand, int32_t* cand,
+                   int32_t* active, int32_t* n_active, void* stream);
+size_t fwav_sim_topk_dim_workspace_size(int64_t max_q, int64_t n_domains, int emb_dim, int k);
+int fwav_sim_topk_dim(const float* emb, const void* embh, int64_t n_domains, int emb_dim, const int32_t* active,
+                      const int32_t* n_active, int64_t max_q, int64_t q_offset, int k, int blas_threads,
+                      int32_t* cand, int32_t* ties, void* workspace, size_t ws_bytes, void* stream);
+int fwav_score_rows_dim(const float* emb, int64_t n_domains, int emb_dim, const int32_t* rows, int64_t n_rows,
+                        int64_t q_offset, int blas_threads, float* scores, void* stream);
+int fwav_tie_check_dim(const float* ranges, int64_t n_ranges, int range_size, const int32_t* cand, int k,
+                       const float* pool, int64_t n_domains, const float* emb, int emb_dim, int64_t q_offset,
+                       int blas_threads, const int32_t* ties, int64_t max_ties, int exact_sets, int32_t* resolve,
+                       void* stream);
+int fwav_debug_score_dim(const float* d, const float* q, int emb_dim, int kind, float* out);
+
 /* ------------------------------------------------------------------- decompression loop
  * Replaces decompress_audio (fractal.py:1378-1473).  recon values are bit-exact with the reference.
  * fwav_decode runs the whole loop on one device with no host synchronisation: up to 64 iterations per launch
