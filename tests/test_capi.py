@@ -78,6 +78,12 @@ def test_every_knob_is_guarded():
         guard = guard[:guard.index("#error")]
         named = set(re.findall(r"defined\((" + pre + r"\w+)\)", guard))
         assert knobs and knobs <= named, (f, sorted(knobs - named))
+    # the search's private headers define no switch: one moved there would escape the guard above
+    import glob
+    heads = sorted(glob.glob(os.path.join(ROOT, "audio-compression_amd", "csrc", "fwav_topk*.h")))
+    assert heads
+    for h in heads:
+        assert not re.findall(r"#\s*ifn?def\s+(?:FWAV_TOPK_|FWAV_FLOOR_)\w*", open(h).read()), h
 
 
 @pytest.mark.parametrize("switch", ["FWAV_TOPK_ABL=1", "FWAV_TOPK_CPMIN=4", "FWAV_TOPK_W=4", "FWAV_TOPK_G=2",
