@@ -55,6 +55,8 @@ SIGNATURES = {
     "fwav_tie_rows_in": (I32, [P, I64, P, I32, P, P, I32, P, P]),
     "fwav_tie_rows_out": (I32, [P, I64, P, P, P, P, P, P, P, P, P, P, P]),
     "fwav_tie_list_size": (I64, [I64]),
+    "fwav_compact_workspace_size": (SZ, [I64, I64]),
+    "fwav_compact_domains": (I32, [P, I64, P, I64, I32, P, P, P, P, P, SZ, P]),
     "fwav_emb16_from_emb": (I32, [P, I64, P, P]),
     "fwav_embh_elems": (SZ, [I64, I32]),
     "fwav_embh_from_emb": (I32, [P, I64, I32, P, P]),
@@ -98,6 +100,7 @@ DEBUG_SIGNATURES = {
     "fwav_debug_topk_floor": (I32, [I32, F32]),
     "fwav_debug_topk_floor_pieces": (I32, [I32]),
     "fwav_debug_sim_topk_layout": (I32, [I64, I64, P]),
+    "fwav_debug_compact_stage_ms": (I32, [P, I64, P, I64, I32, P, P, P, P, P, SZ, P, P]),
 }
 
 

@@ -46,22 +46,50 @@ def _default_k():
 def compress_audio(signal, framerate, sampwidth, tile_size=1024, emb_dim=16, top_k=None, ef_search=50, use_gpu=False,
                    energy_thresh=1e-4, domains_tmpdir=None, batch_size_gpu=512, batch_size_cpu=128, fast_mode=True,
                    transient_weight=1.0, n_mels=40, cpu_workers=None, batch_size=None, device=None,
-                   embedding="matrix"):
+                   embedding="matrix", compact=False):
     """fractal.py:1045 — returns ``(matches, domains, n_ranges, range_size, tile_size, domain_step,
     energy_thresh, original_len)``.  ``embedding`` as :func:`fwav.engine.compress_device`: "pocketfft" embeds with
     scipy's own DCT sequence at every supported range size (ValueError at the others), so that tiles of 4352 samples
     and more give the reference's matches too.  ``emb_dim``: 16 (default) or 32, the reference's rows of two heads
-    of 16 coefficients (with embedding="matrix"; "pocketfft" is ValueError there); NotImplementedError otherwise."""
+    of 16 coefficients (with embedding="matrix"; "pocketfft" is ValueError there); NotImplementedError otherwise.
+    ``compact=True`` returns only the domain rows that some match names, ``domains`` of shape (m, range_size) in
+    ascending order of their original index, with ``matches.idx`` renumbered to them (:func:`compact_matches`): the
+    same tuple otherwise, it saves and decodes like the full one, and only the m kept rows cross to the host."""
     engine.check_emb_dim(emb_dim, embedding)  # 16 or 32; NotImplementedError for any other width
     k = _default_k() if top_k is None else int(top_k)
     dev = engine.require_device(device)
     sig = np.asarray(signal, dtype=np.float32)
     rs, step = engine.geometry(tile_size)
     t = torch.from_numpy(np.ascontiguousarray(sig)).to(dev)
+    if compact:  # the full pool never leaves the device: no side-stream copy of it
+        res = engine.compress_device(t, tile_size, k, energy_thresh=energy_thresh, fast_mode=fast_mode,
+                                     embedding=embedding, emb_dim=emb_dim)
+        return device_result_to_tuple(engine.compact_device(res), pinned_pool=True)
     copy = _PoolCopy(dev)
     res = engine.compress_device(t, tile_size, k, energy_thresh=energy_thresh, fast_mode=fast_mode,
                                  on_pool=copy.start, embedding=embedding, emb_dim=emb_dim)
     return device_result_to_tuple(res, copy)
+
+
+def compact_matches(matches, domains, device=None):
+    """An already compressed set with only the domain rows its matches name: returns ``(MatchList, domains)`` with
+    ``domains`` = the referenced rows in ascending order of their index, shape (m, range_size), and the match indices
+    renumbered to them; s, o, sym and err are unchanged.  decompress_audio of the result equals that of the input bit
+    for bit (it reads domains[idx] alone, fractal.py:1414), and save_compressed writes a valid, smaller version-1
+    file (fractal.py:1278-1322).  Negative indices stay; when every index is negative, row 0 is kept so that the file
+    still loads.  Idempotent.  IndexError for an index >= len(domains).  Runs on the device (fwav_compact_domains)."""
+    dev = engine.require_device(device)
+    idx, s, o, sym, err = as_match_arrays(matches)
+    dom = np.ascontiguousarray(np.asarray(domains, dtype=np.float32))
+    if len(idx) == 0:
+        return MatchList(idx, s, o, sym, err), dom
+    if dom.ndim != 2 or dom.shape[0] == 0:
+        raise ValueError("domains must be (n_domains, range_size) with at least one row")
+    nd, rs = dom.shape
+    ti = torch.from_numpy(np.ascontiguousarray(idx, dtype=np.int32)).to(dev)
+    tp = torch.from_numpy(dom.reshape(-1)).to(dev)
+    idx_c, pool_c, _, m = engine.compact_arrays(ti, tp, nd, rs)
+    return MatchList(idx_c.cpu().numpy(), s, o, sym, err), pool_c.view(m, rs).cpu().numpy()
 
 
 _side_streams: dict = {}
@@ -94,19 +122,24 @@ class _PoolCopy:
         return self.host.numpy()
 
 
-def device_result_to_tuple(res: "engine.DeviceCompressed", pool_copy: "_PoolCopy | None" = None):
+def device_result_to_tuple(res: "engine.DeviceCompressed", pool_copy: "_PoolCopy | None" = None,
+                           pinned_pool: bool = False):
+    """The reference's 8-tuple from a device result.  ``pinned_pool`` (the compact path, whose pool is known only
+    after the matches): the pool rows go to a pinned buffer in the same batch of copies as the match arrays."""
     rs, tile, step, thr, orig = res.range_size, res.tile_size, res.domain_step, res.energy_thresh, res.original_len
     empty = ([], np.zeros((0, rs), dtype=np.float32), 0, rs, tile, step, thr, orig)
     if res.empty or res.is_silent():
         return empty
     # the five match arrays into pinned buffers, one synchronisation for all of them
-    src = (res.idx, res.s, res.o, res.sym, res.err)
+    src = (res.idx, res.s, res.o, res.sym, res.err) + ((res.pool,) if pinned_pool else ())
     hs = [torch.empty(t.numel(), dtype=t.dtype, pin_memory=True) for t in src]
     for h, t in zip(hs, src):
         h.copy_(t, non_blocking=True)
     torch.cuda.current_stream(res.idx.device).synchronize()
-    matches = MatchList(*[h.numpy() for h in hs])
-    if pool_copy is not None and pool_copy.done is not None:
+    matches = MatchList(*[h.numpy() for h in hs[:5]])
+    if pinned_pool:
+        domains = hs[5].numpy().reshape(res.n_domains, rs)
+    elif pool_copy is not None and pool_copy.done is not None:
         domains = pool_copy.result().reshape(res.n_domains, rs)
     else:
         domains = res.pool.view(res.n_domains, rs).cpu().numpy()
@@ -156,9 +189,9 @@ def compute_snr(original, reconstructed):
 
 
 def process_file_compress(path, outdir=None, tile=1024, energy_thresh=1e-4, use_gpu=False, embedding="matrix",
-                          emb_dim=16):
-    """fractal.py:1491-1521 (the positional CLI OUTPUT is used as a directory, quirk Q8).  ``embedding`` and
-    ``emb_dim`` as :func:`compress_audio`."""
+                          emb_dim=16, compact=False):
+    """fractal.py:1491-1521 (the positional CLI OUTPUT is used as a directory, quirk Q8).  ``embedding``,
+    ``emb_dim`` and ``compact`` as :func:`compress_audio`."""
     try:
         start = time.time()
         signal, framerate, sampwidth = read_wav_mono(path)
@@ -166,7 +199,7 @@ def process_file_compress(path, outdir=None, tile=1024, energy_thresh=1e-4, use_
             signal = np.clip(signal.astype(np.float32), -1.0, 1.0)
         matches, domains, n_ranges, range_size, tile_size, domain_step, energy_threshold, original_len = \
             compress_audio(signal, framerate, sampwidth, tile_size=tile, energy_thresh=energy_thresh, use_gpu=use_gpu,
-                           embedding=embedding, emb_dim=emb_dim)
+                           embedding=embedding, emb_dim=emb_dim, compact=compact)
         logger.info(f"Processed {len(matches)} ranges, domain matrix shape {domains.shape}")
         if outdir and not os.path.exists(outdir):
             os.makedirs(outdir)
@@ -182,6 +215,30 @@ def process_file_compress(path, outdir=None, tile=1024, energy_thresh=1e-4, use_
         return {"input": path, "output": outpath, "time_s": elapsed, "ratio": ratio}
     except Exception as e:  # noqa: BLE001 — the reference returns an error dict, never raises
         logger.exception("Compression failed for %s", path)
+        return {"input": path, "error": str(e)}
+
+
+def process_file_compact(path, out=None):
+    """Re-pack an existing .fwav with only the domain rows its matches name (:func:`compact_matches`); framerate,
+    sampwidth, tile, step, threshold and original_len are carried over.  ``out`` is the output file (default: ``path``
+    with ".compact.fwav" in place of ".fwav").  Returns a dict like :func:`process_file_compress`'s."""
+    try:
+        start = time.time()
+        (matches, domains, n_ranges, range_size, framerate, sampwidth, tile_size, domain_step, energy_threshold,
+         original_len) = load_compressed(path)
+        cm, cd = compact_matches(matches, domains)
+        outpath = out or ((path[:-len(".fwav")] if path.endswith(".fwav") else path) + ".compact.fwav")
+        outdir = os.path.dirname(outpath)
+        if outdir and not os.path.exists(outdir):
+            os.makedirs(outdir)
+        save_compressed(outpath, cm, cd, range_size, framerate, sampwidth, tile_size, domain_step, energy_threshold,
+                        original_len)
+        elapsed = time.time() - start
+        logger.info(f"Compacted {path} -> {outpath}  domain rows {len(domains)} -> {len(cd)}  time={elapsed:.2f}s")
+        return {"input": path, "output": outpath, "time_s": elapsed, "n_domains": int(len(domains)),
+                "n_domains_kept": int(len(cd)), "ratio": os.path.getsize(path) / os.path.getsize(outpath)}
+    except Exception as e:  # noqa: BLE001 — as the other file-level entry points: an error dict, never a raise
+        logger.exception("Compaction failed for %s", path)
         return {"input": path, "error": str(e)}
 
 

@@ -2,9 +2,14 @@
 
   python fractal.py compress IN OUT [--tile 1024] [--energy-thresh 1e-4] [--gpu] [--batch] [--out DIR] [--workers 4]
                             [--embedding {matrix,pocketfft}] [--emb-dim {16,32}]
+                            [--compact]
   python fractal.py decompress IN [--out PATH] [--iter 8] [--eps 1e-3] [--gpu] [--batch] [--workers 4]
+  python fractal.py compact IN.fwav [--out PATH]
 
---embedding and --emb-dim are this port's extra flags.  --emb-dim is compress_audio's emb_dim (the reference's CLI
+--embedding, --emb-dim, --compact and the compact sub-command are this port's extras.  --compact stores only the
+domain rows that some match names, with the match indices renumbered: a valid version-1 file, a fraction of the size,
+that any decoder of the format reads to the same samples; `compact` re-packs an existing file that way (default output:
+IN with .compact.fwav in place of .fwav).  --emb-dim is compress_audio's emb_dim (the reference's CLI
 never passes it): 32 embeds with two heads of 16 coefficients.  --embedding "pocketfft" embeds with scipy's own DCT sequence at every supported range
 size (tiles of 4352 samples and more then give the reference's file too); the default "matrix" is bit-exact at range
 sizes 4, 8 and 16.  Non-batch OUTPUT / --out are used as directories (quirk Q8, fractal.py:1509, 1538).  Batch mode skips
@@ -32,6 +37,11 @@ def _compress_job(args):
 def _decompress_job(args):
     from .api import process_file_decompress
     return process_file_decompress(*args)
+
+
+def _compact_job(args):
+    from .api import process_file_compact
+    return process_file_compact(*args)
 
 
 def _pin_device(counter, n_gpus):
@@ -66,7 +76,7 @@ def _run_pool(job, argsets, workers):
         return pool.map(job, argsets, chunksize=1)
 
 
-def main(argv=None):
+def build_parser() -> argparse.ArgumentParser:
     parser = argparse.ArgumentParser(description="Fractal WAV compressor with GPU, batch processing, and metrics")
     sub = parser.add_subparsers(dest="cmd")
     pc = sub.add_parser("compress")
@@ -83,6 +93,11 @@ def main(argv=None):
                          "sequence (bit-exact at every supported range size; an unsupported one is an error)")
     pc.add_argument("--emb-dim", type=int, choices=(16, 32), default=16,
                     help="embedding width (compress_audio's emb_dim): two heads of 8 or of 16 DCT coefficients")
+    pc.add_argument("--compact", action="store_true",
+                    help="store only the domain rows that some match names (a smaller, valid .fwav)")
+    pk = sub.add_parser("compact")
+    pk.add_argument("input", help="input FWAV file")
+    pk.add_argument("--out", default=None, help="output FWAV file (default: IN with .compact.fwav for .fwav)")
     pd = sub.add_parser("decompress")
     pd.add_argument("input", help="input file or directory")
     pd.add_argument("--out", default=None, help="output file or directory")
@@ -91,14 +106,21 @@ def main(argv=None):
     pd.add_argument("--gpu", action="store_true")
     pd.add_argument("--batch", action="store_true", help="treat input as directory and decompress all FWAV inside")
     pd.add_argument("--workers", type=int, default=4, help="parallel file-level workers for batch")
+    return parser
+
+
+def main(argv=None):
+    parser = build_parser()
     args = parser.parse_args(argv)
 
+    if args.cmd == "compact":
+        return _compact_job((args.input, args.out))
     if args.cmd == "compress":
         if not args.batch:
             if args.output is None:
                 parser.error("compress requires OUTPUT unless --batch is used")
             return _compress_job((args.input, args.output, args.tile, args.energy_thresh, args.gpu, args.embedding,
-                                  args.emb_dim))
+                                  args.emb_dim, args.compact))
         if args.output is not None:
             parser.error("Do not provide positional OUTPUT when using --batch; use --out instead")
         out_dir = args.out or args.input
@@ -109,7 +131,7 @@ def main(argv=None):
             logger.info("No files to compress — all already exist.")
             return None
         results = _run_pool(_compress_job, [(f, os.path.join(out_dir, os.path.basename(f) + ".fwav"), args.tile,
-                                             args.energy_thresh, args.gpu, args.embedding, args.emb_dim)
+                                             args.energy_thresh, args.gpu, args.embedding, args.emb_dim, args.compact)
                                             for f in todo],
                             args.workers)
         metrics_file = os.path.join(out_dir, "compression_metrics.json")

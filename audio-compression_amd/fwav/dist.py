@@ -270,13 +270,16 @@ def compress_sharded_finish(h: dict):
 
 def compress_sharded(signal: Optional[np.ndarray], tile_size: int, top_k: int, energy_thresh: float = 1e-4,
                      group=None, device: Optional[torch.device] = None, compute: Optional[Callable] = None,
-                     embedding: str = "matrix", emb_dim: int = 16):
+                     embedding: str = "matrix", emb_dim: int = 16, compact: bool = False):
     """Compress one signal with its ranges split across the ranks of ``group``.
 
     ``signal`` is read on rank 0 only (other ranks may pass None).  Returns, on rank 0, a dict with the
     full SoA match arrays (numpy), ``pool`` (numpy [n_domains, range_size]), n_ranges, range_size,
     domain_step, original_len, and the per-rank blocks; other ranks return None.  ``embedding`` and
-    ``emb_dim`` as :func:`compress_sharded_start` (the same on every rank).
+    ``emb_dim`` as :func:`compress_sharded_start` (the same on every rank).  ``compact=True``: rank 0 keeps only the
+    domain rows that the gathered matches name (engine.compact_arrays, on its device, before the pool is copied to
+    the host): ``pool`` is then [m, range_size], ``idx`` renumbered, ``kept`` the rows' original indices; a shard's
+    own matches do not determine that set, so the other ranks do nothing more than without it.
     """
     rank = dist.get_rank(group)
     if device is None:
@@ -290,8 +293,20 @@ def compress_sharded(signal: Optional[np.ndarray], tile_size: int, top_k: int, e
         return None
     if out.get("empty") and "idx" not in out:
         return out
+    silent = bool(out.pop("is_silent")())
+    kept = None
+    if compact and not silent and out["n_ranges"] > 0:
+        from .engine import compact_arrays
+        rs_ = out["range_size"]
+        pool = out["pool"]
+        pool = pool if isinstance(pool, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(pool, np.float32))
+        pool = pool.to(device).reshape(-1)
+        out["idx"], out["pool"], kept, _ = compact_arrays(out["idx"].to(device=device, dtype=torch.int32), pool,
+                                                          pool.numel() // rs_, rs_)
     host = {f: out[f].cpu().numpy() for f in FIELDS}
-    host["empty"] = bool(out.pop("is_silent")())
+    host["empty"] = silent
+    if kept is not None:
+        host["kept"] = kept.cpu().numpy()
     pool = out["pool"]
     pool = pool.cpu().numpy() if isinstance(pool, torch.Tensor) else np.asarray(pool)
     host.update({k: v for k, v in out.items() if k not in FIELDS and k != "pool"})

@@ -13,6 +13,7 @@ Reference map (``/root/reference/fractal.py``):
   the same stages on rows of emb_dim = 32 columns (:275)   → fwav_pool_embed_dim, fwav_prune_dim, fwav_sim_topk_dim, …
   _process_gpu_batch :757-850                              → fwav_affine
   decompress_audio :1378-1473                              → fwav_decode
+  (no counterpart; opt-in) the pool rows that :1414 reads   → fwav_compact_domains (compact_device / compact_arrays)
 """
 from __future__ import annotations
 
@@ -175,6 +176,7 @@ class DeviceCompressed:
     pending: Optional[object] = None  # deferred tie resolution (compress_device(defer_ties=True)): a Future
     apply: Optional[object] = None    # ... and its last step, run by wait() on the call's own stream
     stream: Optional[object] = None   # the torch stream the call's kernels were queued on
+    kept: Optional[torch.Tensor] = None  # compact_device: the original index of each pool row, int32[n_domains]
 
     def wait(self) -> "DeviceCompressed":
         """Complete a deferred tie resolution (no-op otherwise); the outputs are final afterwards.  The fix-up runs on
@@ -545,6 +547,52 @@ def _search_sub_blocks(nsub, m, nd, k, lo, rs, threads, sc, tie_order, emb, emb1
         _mark(events, "ties")
     # one tie list in fwav_sim_topk's layout (count, then the records of every slice)
     return torch.cat([torch.tensor([n_ties], dtype=torch.int32, device=dev)] + lists)
+
+
+def compact_arrays(idx: torch.Tensor, pool: torch.Tensor, n_domains: int, range_size: int):
+    """fwav_compact_domains on ``idx``'s device and current stream: the domain rows that ``idx`` (int32[n_ranges])
+    names, in ascending order, and ``idx`` renumbered to them (fractal.py:1278-1322, 1414: the decoder reads
+    domains[idx[i]] alone and the file carries its own n_domains).  Returns (idx_out int32[n_ranges], pool_out
+    f32[m·rs], kept int32[m], m); when every entry is negative, row 0 is kept (m = 1).  One host synchronisation:
+    the 16-byte read of the counts.  IndexError for an entry >= n_domains, as decompress_audio raises it."""
+    if idx.dtype != torch.int32 or pool.dtype != torch.float32 or not idx.is_cuda or pool.device != idx.device:
+        raise ValueError("compact_arrays expects int32 indices and a float32 pool on one HIP device")
+    dev = idx.device
+    nr, nd, rs = idx.numel(), int(n_domains), int(range_size)
+    if pool.numel() < nd * rs:
+        raise ValueError("pool holds fewer than n_domains rows")
+    with torch.cuda.device(dev):
+        idx, pool = idx.contiguous(), pool.contiguous()
+        cap = min(nd, max(nr, 1))
+        idx_out = torch.empty(nr, dtype=torch.int32, device=dev)
+        pool_out = torch.empty(cap * rs, dtype=torch.float32, device=dev)
+        kept = torch.empty(cap, dtype=torch.int32, device=dev)
+        counts = torch.empty(2, dtype=torch.int64, device=dev)
+        wsn = size_call("fwav_compact_workspace_size", nd, nr)
+        ws = torch.empty(wsn, dtype=torch.uint8, device=dev)
+        call("fwav_compact_domains", idx.data_ptr(), nr, pool.data_ptr(), nd, rs, idx_out.data_ptr(),
+             pool_out.data_ptr(), kept.data_ptr(), counts.data_ptr(), ws.data_ptr(), wsn, _stream(dev))
+        m, over = (int(v) for v in counts.cpu())
+    if over:
+        raise IndexError("domain index out of range")
+    return idx_out, pool_out[:m * rs], kept[:m], m
+
+
+def compact_device(res: DeviceCompressed) -> DeviceCompressed:
+    """``res`` with its pool cut down to the rows its matches name: ``pool`` f32[m·rs], ``idx`` renumbered,
+    ``n_domains`` = m and ``kept`` int32[m], the original index of each kept row (so pool == old pool[kept]); s, o,
+    sym and err are the same tensors.  A new result: ``res`` itself is left as it is, and whatever it carries of the
+    search (emb, cand, ties) still counts domains in the original numbering.  Waits for a deferred tie resolution
+    first (the fix-ups change idx).  ValueError for a shard (its matches do not determine the referenced set: compact
+    after the gather); an empty or silent result passes through unchanged."""
+    res.wait()
+    if tuple(res.shard) != (0, res.n_ranges):
+        raise ValueError(f"compact_device needs every range's match: this result is the shard {tuple(res.shard)} of "
+                         f"{res.n_ranges} ranges")
+    if res.empty or res.n_ranges == 0 or res.is_silent():
+        return res
+    idx, pool, kept, m = compact_arrays(res.idx, res.pool, res.n_domains, res.range_size)
+    return dataclasses.replace(res, idx=idx, pool=pool, kept=kept, n_domains=m)
 
 
 def decompress_device(idx: torch.Tensor, *args, **kwargs):

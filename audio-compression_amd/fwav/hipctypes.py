@@ -164,7 +164,7 @@ def _i32(buf: DeviceBuffer, count: int) -> np.ndarray:
 
 def compress(signal: np.ndarray, tile_size: int, top_k: int, energy_thresh: float = 1e-4, fast_mode: bool = True,
              s_clip: float = 16.0, tie_order: str = "numpy", threads: int | None = None,
-             embedding: str = "matrix", emb_dim: int = 16) -> dict | None:
+             embedding: str = "matrix", emb_dim: int = 16, compact: bool = False) -> dict | None:
     """compress_audio's device pipeline (fractal.py:1040-1256) with HIP buffers only, on the null stream:
 
       fwav_voiced_ranges → fwav_weighted_energy (silent test, :1083) → fwav_pool_embed → fwav_prune → fwav_sim_topk
@@ -179,7 +179,10 @@ def compress(signal: np.ndarray, tile_size: int, top_k: int, energy_thresh: floa
     (fwav_pool_embed_exact: scipy's DCT sequence at every supported range size, ValueError at the others).
     ``emb_dim=32`` runs the same sequence through the ``*_dim`` entry points (fwav_pool_embed_dim, fwav_prune_dim,
     fwav_sim_topk_dim, fwav_tie_check_dim, fwav_score_rows_dim) on rows of 32 columns (emb f32[nd, 32]); it needs
-    embedding="matrix" (ValueError otherwise), and any width but 16 and 32 is NotImplementedError."""
+    embedding="matrix" (ValueError otherwise), and any width but 16 and 32 is NotImplementedError.
+    ``compact=True`` ends the sequence with fwav_compact_domains: ``pool`` then holds only the m rows that the matches
+    name (f32[m, rs], ascending original index), ``idx`` is renumbered to them, ``n_domains`` = m, and ``kept``
+    i32[m] gives each row's original index (``emb`` and ``cand`` keep the original numbering)."""
     if emb_dim not in (16, 32):
         raise NotImplementedError(f"emb_dim={emb_dim!r}: the MI355X engine supports emb_dim 16 and 32")
     if emb_dim != 16 and embedding == "pocketfft":
@@ -284,12 +287,30 @@ def compress(signal: np.ndarray, tile_size: int, top_k: int, energy_thresh: floa
             call("fwav_affine", d_rsub.value, n_res, rs, d_newc.value, k, d_pool.value, nd, sc, *[b.value for b in tmp],
                  None)
             call("fwav_tie_rows_out", d_rows.value, n_res, *[b.value for b in tmp], *[b.value for b in outs], None)
+    kept, nd_out = None, nd
+    if compact:
+        # after the tie fix-ups (they change idx): only the rows that the matches name, indices renumbered in place
+        cap = min(nd, max(nr, 1))
+        d_cpool, d_kept, d_counts = DeviceBuffer(4 * cap * rs), DeviceBuffer(4 * cap), DeviceBuffer(16)
+        wsc = size_call("fwav_compact_workspace_size", nd, nr)
+        d_wsc = DeviceBuffer(wsc)
+        call("fwav_compact_domains", outs[0].value, nr, d_pool.value, nd, rs, outs[0].value, d_cpool.value,
+             d_kept.value, d_counts.value, d_wsc.value, wsc, None)
+        call("fwav_stream_sync", None)
+        nd_out, over = (int(v) for v in d_counts.to_array(np.int64, 2))
+        if over:
+            raise IndexError("domain index out of range")
+        kept = _i32(d_kept, nd_out)
+        d_pool = d_cpool
     call("fwav_stream_sync", None)
-    return dict(idx=_i32(outs[0], nr), s=outs[1].to_array(np.float32, nr), o=outs[2].to_array(np.float32, nr),
-                sym=outs[3].to_array(np.uint8, nr), err=outs[4].to_array(np.float32, nr),
-                pool=d_pool.to_array(np.float32, nd * rs).reshape(nd, rs),
-                emb=d_emb.to_array(np.float32, nd * dim).reshape(nd, dim), cand=_i32(d_cand, nr * k).reshape(nr, k),
-                n_ranges=nr, range_size=rs, domain_step=step, n_domains=nd, n_ties=n_ties, n_resolved=n_res)
+    out = dict(idx=_i32(outs[0], nr), s=outs[1].to_array(np.float32, nr), o=outs[2].to_array(np.float32, nr),
+               sym=outs[3].to_array(np.uint8, nr), err=outs[4].to_array(np.float32, nr),
+               pool=d_pool.to_array(np.float32, nd_out * rs).reshape(nd_out, rs),
+               emb=d_emb.to_array(np.float32, nd * dim).reshape(nd, dim), cand=_i32(d_cand, nr * k).reshape(nr, k),
+               n_ranges=nr, range_size=rs, domain_step=step, n_domains=nd_out, n_ties=n_ties, n_resolved=n_res)
+    if compact:
+        out["kept"] = kept
+    return out
 
 
 def decompress(idx: np.ndarray, s: np.ndarray, o: np.ndarray, sym: np.ndarray, pool: np.ndarray, n_ranges: int,

@@ -184,6 +184,32 @@ int fwav_tie_rows_out(const int32_t* rows, int64_t n, const int32_t* idx_in, con
  * sink: one float of device memory. */
 int fwav_debug_gather_rows(const float* table, int64_t n_rows, int rs, int64_t n, float* sink, void* stream);
 
+/* ------------------------------------------------------------------- compact domain pool
+ * Keeps only the domain rows that some match names and renumbers the matches.  decompress_audio reads
+ * domains[idx[i]] and nothing else (fractal.py:1414), and a .fwav stores its own n_domains (save_compressed /
+ * load_compressed, fractal.py:1278-1322), so the compact set is a valid version-1 file that decodes to the same
+ * samples.  Opt-in: no other entry point calls it.
+ *   u = the ascending distinct values of idx[0 .. n_ranges) that lie in [0, n_domains), m = len(u); when n_ranges > 0
+ *     and m == 0 (every entry negative) u = [0], m = 1: a file with no domain row cannot be loaded (np.vstack([]) in
+ *     the reference's load_compressed), and the decoder indexes row 0 for a −1 entry before it zeroes the range.
+ *   pool_out[j·range_size ..] = pool[u[j]·range_size ..] bit for bit, j < m; the caller provides
+ *     min(n_domains, max(n_ranges, 1)) rows, and rows from m on are not written.  Rows are range_size floats with no
+ *     alignment beyond 4 B (range sizes 5 and 19 are as good as 8).
+ *   idx_out[i] = the position of idx[i] in u; a negative idx[i] is copied unchanged.  idx_out may be idx itself.
+ *   kept (may be NULL) int32[as many as pool_out has rows]: kept[j] = u[j], j < m.
+ *   counts int64[2]: counts[0] = m, counts[1] = the number of entries >= n_domains.  Those are never marked, are copied
+ *     to idx_out unchanged and cause no access outside the arrays; the host turns counts[1] != 0 into
+ *     IndexError("domain index out of range"), as decompress_audio would.
+ * n_ranges == 0 writes counts = {0, 0} only (the arrays may be NULL).  1 ≤ range_size ≤ 64; n_domains ≥ 1 when there
+ * are matches.  `ws`: fwav_compact_workspace_size(n_domains, n_ranges) bytes, 8-B aligned (a bitmap of 64-bit words,
+ * one bit per domain, and its per-word and per-scan-block exclusive counts; a scan block is 1024 words = 65,536
+ * domains; non-decreasing in both arguments), FWAV_ERR_WORKSPACE when short.  Six launches (zero, mark, count, scan,
+ * gather, renumber), no workgroup waits on another, integer atomics only: deterministic.  Cost: DESIGN.md §3.7. */
+size_t fwav_compact_workspace_size(int64_t n_domains, int64_t n_ranges);
+int fwav_compact_domains(const int32_t* idx, int64_t n_ranges, const float* pool, int64_t n_domains, int range_size,
+                         int32_t* idx_out, float* pool_out, int32_t* kept, int64_t* counts, void* ws, size_t ws_bytes,
+                         void* stream);
+
 /* ------------------------------------------------------------------- emb_dim = 32 (wide embeddings)
  * compress_audio(emb_dim=32): the reference builds each embedding row from two heads of emb_dim / 2 coefficients
  * (fractal.py:275, 166-208, 154-164), so a row is [tonal: min(16, range_size − 1) values, zero-padded to 16]

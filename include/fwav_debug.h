@@ -83,6 +83,12 @@ int fwav_debug_topk_floor_pieces(int pieces);
  * bitmap), pilot, total (= fwav_sim_topk_workspace_size).  Every region before `pilot` sits at the same offset in
  * libfwav.so; the product library adds the pilots' scores only where its floor can run. */
 int fwav_debug_sim_topk_layout(int64_t max_q, int64_t n_domains, int64_t* offsets);
+/* Diagnostic (tools/compact_bench.py): fwav_compact_domains (same arguments, same outputs, n_ranges > 0) with a HIP
+ * event recorded between its launches; synchronises on the last one.  ms (host float[6]) = the time of the zero, mark,
+ * count, scan, gather and renumber launches. */
+int fwav_debug_compact_stage_ms(const int32_t* idx, int64_t n_ranges, const float* pool, int64_t n_domains,
+                                int range_size, int32_t* idx_out, float* pool_out, int32_t* kept, int64_t* counts,
+                                void* ws, size_t ws_bytes, void* stream, float* ms);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,365 @@
+"""GPU: fwav_compact_domains against its numpy restatement (tests/test_compact_cpu.py restate), bit for bit and with
+poisoned guard regions, and the compact option end to end: compress_audio, compact_matches, the CLI, the torch-free
+binding and two ranks sharing the GPU.  The decoder reads domains[idx[i]] alone (fractal.py:1414) and a .fwav carries
+its own n_domains (fractal.py:1278-1322), so every compact result must decode to exactly the full one's samples."""
+import os
+import socket
+import struct
+import sys
+
+import numpy as np
+import pytest
+
+from golden_util import bit_equal, load
+from test_compact_cpu import SCAN_DOMAINS, restate
+
+torch = pytest.importorskip("torch")
+pytestmark = pytest.mark.gpu
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+POISON = 0x5EEDBEEF  # as int32 and, bit for bit, as float32
+GUARD = 64
+N_DOMAINS = [1, 63, 64, 65, 127, 128, 129, SCAN_DOMAINS - 1, SCAN_DOMAINS, SCAN_DOMAINS + 1, 2 * SCAN_DOMAINS - 1,
+             2 * SCAN_DOMAINS, 2 * SCAN_DOMAINS + 1, 1_000_003]
+RANGE_SIZES = [4, 5, 8, 16, 19, 32, 64]
+N_RANGES = [1, 64, 257, 100_000]
+E2E = ["tone", "sweep", "noise2048", "speech4096", "t1300", "t5000", "t8192"]
+
+_pool_cache: dict = {}
+
+
+def _pool(nd, rs):
+    """nd rows of rs random float32 bit patterns on the device (one table alive at a time)."""
+    if (nd, rs) not in _pool_cache:
+        _pool_cache.clear()
+        gen = torch.Generator(device="cuda").manual_seed(nd * 131 + rs)
+        _pool_cache[(nd, rs)] = torch.randint(-2 ** 31, 2 ** 31 - 1, (nd * rs,), dtype=torch.int32, device="cuda",
+                                              generator=gen)
+    return _pool_cache[(nd, rs)]
+
+
+def patterns(nd, nr, rng):
+    """name → idx int32[nr]: the index patterns of one (n_domains, n_ranges) pair."""
+    words = -(-nd // 64)
+    w = np.arange(nr) % words
+    neg = rng.integers(0, nd, nr)
+    cut = rng.random(nr)
+    neg = np.where(cut < 0.15, -1, np.where(cut < 0.30, -rng.integers(2, 2 ** 31, nr), neg))
+    over = rng.integers(0, nd, nr)
+    over[rng.integers(0, nr, min(nr, 5))] = nd
+    over[rng.integers(0, nr)] = 2 ** 31 - 1
+    if nr > 2:
+        over[rng.integers(0, nr)] = nd + 1
+    return {"all_negative": np.full(nr, -1), "first": np.zeros(nr), "last": np.full(nr, nd - 1),
+            "one_per_word": np.minimum(w * 64 + (w * 7) % 64, nd - 1), "all_equal": np.full(nr, rng.integers(0, nd)),
+            "negatives": neg, "over": over}
+
+
+def run_kernel(idx, pool, nd, rs, in_place=False):
+    """fwav_compact_domains on idx (numpy int32) → (counts, idx_out, kept buffer, pool_out buffer), outputs with a
+    poisoned guard behind them and poisoned from the first element on."""
+    from fwav._lib import call, size_call
+    nr = len(idx)
+    cap = min(nd, max(nr, 1))
+    dev = pool.device
+    iout = torch.full((nr + GUARD,), POISON, dtype=torch.int32, device=dev)
+    if in_place:
+        iout[:nr] = torch.from_numpy(idx).to(dev)
+        src = iout
+    else:
+        src = torch.from_numpy(idx).to(dev)
+    pout = torch.full(((cap + GUARD) * rs,), POISON, dtype=torch.int32, device=dev)
+    kept = torch.full((cap + GUARD,), POISON, dtype=torch.int32, device=dev)
+    counts = torch.full((2,), -7, dtype=torch.int64, device=dev)
+    wsn = size_call("fwav_compact_workspace_size", nd, nr)
+    ws = torch.full((wsn + GUARD,), 0xA5, dtype=torch.uint8, device=dev)  # a dirty workspace: the call zeroes its own
+    call("fwav_compact_domains", src.data_ptr(), nr, pool.data_ptr(), nd, rs, iout.data_ptr(), pout.data_ptr(),
+         kept.data_ptr(), counts.data_ptr(), ws.data_ptr(), wsn, torch.cuda.current_stream().cuda_stream)
+    assert bool((ws[wsn:] == 0xA5).all()), "workspace guard"
+    return counts.cpu().numpy(), iout, kept, pout
+
+
+def check(idx, pool, nd, rs, in_place=False):
+    idx = np.ascontiguousarray(idx, dtype=np.int32)
+    nr = len(idx)
+    counts, iout, kept, pout = run_kernel(idx, pool, nd, rs, in_place)
+    inside = (idx >= 0) & (idx < nd)
+    u = np.unique(idx[inside]).astype(np.int32)
+    u = np.zeros(1, np.int32) if (len(u) == 0 and nr > 0) else u
+    want_idx = np.where(inside, np.searchsorted(u, idx), idx).astype(np.int32)
+    m = len(u)
+    assert counts.tolist() == [m, int((idx >= nd).sum())]
+    assert np.array_equal(iout[:nr].cpu().numpy(), want_idx)
+    assert bool((iout[nr:] == POISON).all()), "idx_out guard"
+    ud = torch.from_numpy(u).to(pool.device)
+    assert torch.equal(kept[:m], ud)
+    assert bool((kept[m:] == POISON).all()), "kept: entries from m on, and the guard"
+    rows = pool.view(nd, rs)[ud.long()]
+    assert torch.equal(pout[:m * rs].view(m, rs), rows)  # int32 views: bit for bit
+    assert bool((pout[m * rs:] == POISON).all()), "pool_out: rows from m on, and the guard"
+    return m
+
+
+@pytest.mark.parametrize("rs", RANGE_SIZES)
+@pytest.mark.parametrize("nd", N_DOMAINS)
+def test_kernel_matches_restatement(nd, rs):
+    rng = np.random.default_rng(nd * 100 + rs)
+    pool = _pool(nd, rs)
+    for nr in N_RANGES:
+        for name, idx in patterns(nd, nr, rng).items():
+            m = check(idx, pool, nd, rs)
+            if name in ("first", "last", "all_equal", "all_negative"):
+                assert m == 1, name
+            if name == "one_per_word":
+                assert m == min(nr, -(-nd // 64)), name
+    assert check(rng.permutation(nd), pool, nd, rs) == nd  # a permutation naming every domain
+    idx = patterns(nd, 257, rng)["negatives"]
+    check(idx, pool, nd, rs, in_place=True)
+    # the numpy restatement of the CPU tests says the same (one host-side comparison per case)
+    counts, iout, kept, pout = run_kernel(np.ascontiguousarray(idx, np.int32), pool, nd, rs)
+    host_pool = pool.view(nd, rs).cpu().numpy() if nd * rs <= 1 << 22 else None
+    if host_pool is not None:
+        u, cp, ci, over = restate(idx, host_pool)
+        assert counts.tolist() == [len(u), over] and np.array_equal(iout[:257].cpu().numpy(), ci)
+        assert np.array_equal(pout[:len(u) * rs].cpu().numpy().reshape(len(u), rs), cp)
+
+
+def test_no_ranges_writes_counts_only():
+    from fwav._lib import call, size_call
+    counts = torch.full((2,), -7, dtype=torch.int64, device="cuda")
+    wsn = size_call("fwav_compact_workspace_size", 100, 0)
+    ws = torch.empty(wsn, dtype=torch.uint8, device="cuda")
+    call("fwav_compact_domains", None, 0, None, 100, 8, None, None, None, counts.data_ptr(), ws.data_ptr(), wsn,
+         torch.cuda.current_stream().cuda_stream)
+    assert counts.cpu().tolist() == [0, 0]
+
+
+# ------------------------------------------------------------------------------------------------ end to end
+_results: dict = {}
+
+
+def _compressed(case):
+    """(golden, full 8-tuple, compact 8-tuple) of one golden signal, computed once."""
+    if case not in _results:
+        from fwav.api import compress_audio
+        g = load(case)
+        p = g["p"]
+        kw = dict(tile_size=p["tile"], top_k=p["Ks"][0], energy_thresh=p["thr"])
+        full = compress_audio(g["signal"], p["framerate"], p["sampwidth"], **kw)
+        comp = compress_audio(g["signal"], p["framerate"], p["sampwidth"], compact=True, **kw)
+        _results[case] = (g, full, comp)
+    return _results[case]
+
+
+@pytest.mark.parametrize("case", E2E)
+def test_compress_audio_compact(case):
+    from fwav import engine
+    g, full, comp = _compressed(case)
+    p = g["p"]
+    fm, fd = full[0], full[1]
+    cm, cd = comp[0], comp[1]
+    u, want_pool, want_idx, over = restate(fm.idx, fd)
+    assert over == 0 and cd.shape == (len(u), p["rs"]) and cd.dtype == np.float32
+    assert bit_equal(cd, want_pool) and np.array_equal(cm.idx, want_idx)
+    ok = fm.idx >= 0
+    assert bit_equal(cd[cm.idx[ok]], fd[fm.idx[ok]]) and np.array_equal(cm.idx[~ok], fm.idx[~ok])
+    for f in ("s", "o", "sym", "err"):
+        assert bit_equal(getattr(cm, f), getattr(fm, f)), f
+    assert comp[2:] == full[2:]
+    # the engine's result carries the kept rows' original indices
+    sig = torch.from_numpy(g["signal"]).cuda()
+    res = engine.compress_device(sig, p["tile"], p["Ks"][0], energy_thresh=p["thr"])
+    cres = engine.compact_device(res)
+    assert cres.n_domains == len(u) and np.array_equal(cres.kept.cpu().numpy(), u)
+    assert res.n_domains == p["n_domains"] and res.pool.numel() == p["n_domains"] * p["rs"]  # the input is untouched
+    assert bit_equal(cres.pool.cpu().numpy().reshape(-1, p["rs"]), want_pool)
+
+
+@pytest.mark.parametrize("case", E2E)
+def test_decode_and_compact_matches(case):
+    from fwav.api import compact_matches, decompress_audio
+    from fwav.matches import MatchList
+    g, full, comp = _compressed(case)
+    p = g["p"]
+    k = p["Ks"][0]
+    nr, rs = p["n_ranges"], p["rs"]
+    a = decompress_audio(full[0], full[1], nr, rs, original_len=p["original_len"], return_info=True)
+    b = decompress_audio(comp[0], comp[1], nr, rs, original_len=p["original_len"], return_info=True)
+    assert bit_equal(a[0], b[0]) and a[1]["iterations"] == b[1]["iterations"]
+    # compact_matches of the full result is the compact result, and once more changes nothing
+    m1, d1 = compact_matches(full[0], full[1])
+    m2, d2 = compact_matches(m1, d1)
+    for m, d in ((m1, d1), (m2, d2)):
+        assert bit_equal(d, comp[1]) and np.array_equal(m.idx, comp[0].idx)
+        for f in ("s", "o", "sym", "err"):
+            assert bit_equal(getattr(m, f), getattr(comp[0], f)), f
+    # the reference's own matches, compacted, decode to the reference's own reconstruction
+    gm = MatchList(*[g[f"m_{f}_{k}"] for f in ("idx", "s", "o", "sym", "err")])
+    m3, d3 = compact_matches(gm, g["pool"])
+    assert len(d3) == len(restate(gm.idx, g["pool"])[0]) < p["n_domains"]
+    rec, info = decompress_audio(m3, d3, nr, rs, original_len=p["original_len"], return_info=True)
+    assert bit_equal(rec, g[f"dec_{k}"]) and info["iterations"] == int(g[f"dec_iters_{k}"])
+
+
+def _header(path):
+    from fwav.fwavio import HEADER_FMT, HEADER_SIZE
+    with open(path, "rb") as f:
+        return struct.unpack(HEADER_FMT, f.read(HEADER_SIZE))
+
+
+@pytest.mark.parametrize("case", ["sweep", "t1300"])
+def test_cli_compact_files(tmp_path, case):
+    from fwav.cli import main
+    from fwav.fwavio import load_compressed, write_wav
+    g = load(case)
+    p = g["p"]
+    wav = tmp_path / f"{case}.wav"
+    write_wav(str(wav), g["signal"], p["framerate"], p["sampwidth"])
+    r = main(["compress", str(wav), str(tmp_path / "full"), "--tile", str(p["tile"])])
+    assert "error" not in r, r
+    r = main(["compress", str(wav), str(tmp_path / "small"), "--tile", str(p["tile"]), "--compact"])
+    assert "error" not in r, r
+    full = tmp_path / "full" / f"{case}.wav.fwav"
+    small = tmp_path / "small" / f"{case}.wav.fwav"
+    r = main(["compact", str(full), "--out", str(tmp_path / "re" / "packed.fwav")])
+    assert "error" not in r and r["output"] == str(tmp_path / "re" / "packed.fwav"), r
+    assert (tmp_path / "re" / "packed.fwav").read_bytes() == small.read_bytes()
+    hf, hs = _header(full), _header(small)
+    nd, m = hf[9], hs[9]
+    assert hf[:9] == hs[:9] and hf[10] == hs[10] and nd == p["n_domains"] and 0 < m < nd
+    assert os.path.getsize(full) - os.path.getsize(small) == 4 * p["rs"] * (nd - m)
+    # default output name, and a compact file re-packs to itself
+    r = main(["compact", str(full)])
+    assert r["output"] == str(tmp_path / "full" / f"{case}.wav.compact.fwav") and (r["n_domains"], r["n_domains_kept"]) == (nd, m)
+    assert open(r["output"], "rb").read() == small.read_bytes()
+    r = main(["compact", str(small), "--out", str(tmp_path / "again.fwav")])
+    assert (tmp_path / "again.fwav").read_bytes() == small.read_bytes()
+    # both files decompress to the same samples
+    lf, ls = load_compressed(str(full)), load_compressed(str(small))
+    from fwav.api import decompress_audio
+    assert bit_equal(decompress_audio(lf[0], lf[1], lf[2], lf[3], original_len=lf[9]),
+                     decompress_audio(ls[0], ls[1], ls[2], ls[3], original_len=ls[9]))
+
+
+@pytest.mark.parametrize("case", ["tone", "noise2048", "t5000"])
+def test_hipctypes_compact_agrees(case):
+    from fwav import hipctypes as H
+    g, full, comp = _compressed(case)
+    p = g["p"]
+    r = H.compress(g["signal"], p["tile"], p["Ks"][0], energy_thresh=p["thr"], compact=True)
+    u = restate(full[0].idx, full[1])[0]
+    assert r["n_domains"] == len(u) and np.array_equal(r["kept"], u)
+    assert np.array_equal(r["idx"], comp[0].idx) and bit_equal(r["pool"], comp[1])
+    for f in ("s", "o", "sym", "err"):
+        assert bit_equal(r[f], getattr(comp[0], f)), f
+    r0 = H.compress(g["signal"], p["tile"], p["Ks"][0], energy_thresh=p["thr"])
+    assert "kept" not in r0 and np.array_equal(r0["idx"], full[0].idx) and bit_equal(r0["pool"], full[1])
+
+
+def test_silent_signal_returns_the_empty_tuple():
+    from fwav.api import compress_audio
+    a = compress_audio(np.zeros(5000, np.float32), 44100, 4, tile_size=1024)
+    b = compress_audio(np.zeros(5000, np.float32), 44100, 4, tile_size=1024, compact=True)
+    assert len(b[0]) == 0 and b[1].shape == a[1].shape == (0, 4) and b[2:] == a[2:]
+    c = compress_audio(np.ones(100, np.float32), 44100, 4, tile_size=2048, compact=True)  # shorter than a tile
+    assert len(c[0]) == 0 and c[1].shape == (0, 8)
+
+
+def test_all_negative_set_keeps_one_row_and_decodes_to_zeros():
+    from fwav.api import compact_matches, decompress_audio
+    from fwav.matches import MatchList
+    rng = np.random.default_rng(5)
+    nr, rs, nd = 37, 5, 90
+    dom = rng.normal(size=(nd, rs)).astype(np.float32)
+    m = MatchList(np.full(nr, -1), rng.normal(size=nr), rng.normal(size=nr), rng.integers(0, 2, nr), np.zeros(nr))
+    cm, cd = compact_matches(m, dom)
+    assert cd.shape == (1, rs) and bit_equal(cd, dom[:1]) and np.array_equal(cm.idx, m.idx)
+    rec = decompress_audio(cm, cd, nr, rs)
+    assert rec.shape == (nr * rs,) and not rec.any()
+    assert bit_equal(rec, decompress_audio(m, dom, nr, rs))
+
+
+def test_index_out_of_range_raises():
+    from fwav import engine
+    from fwav.api import compact_matches
+    from fwav.matches import MatchList
+    dom = np.ones((10, 8), np.float32)
+    for bad in (10, 11, 2 ** 31 - 1):
+        m = MatchList([3, bad, -1, 9], [1.0] * 4, [0.0] * 4, [0] * 4, [0.0] * 4)
+        with pytest.raises(IndexError, match="domain index out of range"):
+            compact_matches(m, dom)
+    with pytest.raises(IndexError, match="domain index out of range"):
+        engine.compact_arrays(torch.tensor([0, 10], dtype=torch.int32, device="cuda"),
+                              torch.ones(80, dtype=torch.float32, device="cuda"), 10, 8)
+    cm, cd = compact_matches(MatchList([3, 9, -1, 9], [1.0] * 4, [0.0] * 4, [0] * 4, [0.0] * 4), dom)
+    assert cm.idx.tolist() == [0, 1, -1, 1] and cd.shape == (2, 8)
+
+
+# ------------------------------------------------------------------------------------------------ two ranks
+def _free_port():
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    p = s.getsockname()[1]
+    s.close()
+    return p
+
+
+def _worker(rank, world, port, q):
+    sys.path[:0] = [ROOT, os.path.join(ROOT, "audio-compression_amd")]
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    import torch.distributed as dist
+    from fwav import dist as D, engine, synth
+    try:
+        dev = torch.device("cuda", 0)
+        torch.cuda.set_device(dev)
+        dist.init_process_group("gloo", rank=rank, world_size=world)
+        sig = synth.make_config_signal("cfg2", seconds=2.0, seed=3)[0]
+        out = D.compress_sharded(sig if rank == 0 else None, 2048, 64, 1e-4, device=dev, compact=True)
+        if rank == 0:
+            one = engine.compress_device(torch.from_numpy(sig).to(dev), 2048, 64)
+            c = engine.compact_device(one)
+            same = {f: bool(np.array_equal(out[f].view(np.uint8), getattr(c, f).cpu().numpy().view(np.uint8)))
+                    for f in ("idx", "s", "o", "sym", "err")}
+            same["pool"] = bool(np.array_equal(out["pool"].view(np.uint32),
+                                               c.pool.cpu().numpy().reshape(-1, c.range_size).view(np.uint32)))
+            same["kept"] = bool(np.array_equal(out["kept"], c.kept.cpu().numpy()))
+            q.put(dict(same=same, blocks=out["blocks"], rows=(int(out["pool"].shape[0]), c.n_domains, one.n_domains),
+                       empty=out["empty"]))
+        else:
+            q.put(dict(rank1=out))
+        dist.barrier()
+        dist.destroy_process_group()
+    except Exception as e:  # noqa: BLE001
+        q.put(dict(error=repr(e)))
+        raise
+
+
+def test_two_ranks_share_gpu_compact():
+    import queue as _q
+    import torch.multiprocessing as mp
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_worker, args=(r, 2, port, q)) for r in range(2)]
+    for p in procs:
+        p.start()
+    outs = []
+    for _ in range(170):
+        try:
+            outs.append(q.get(timeout=1))
+            if len(outs) == 2:
+                break
+        except _q.Empty:
+            if any(p.exitcode not in (None, 0) for p in procs):
+                break
+    for p in procs:
+        p.join(timeout=30)
+        if p.exitcode is None:
+            p.kill()
+    assert len(outs) == 2 and not any("error" in o for o in outs), outs
+    r0 = next(o for o in outs if "same" in o)
+    assert all(r0["same"].values()), r0["same"]
+    assert r0["rows"][0] == r0["rows"][1] < r0["rows"][2] and not r0["empty"]
+    (a0, b0), (a1, b1) = r0["blocks"]
+    assert a0 == 0 and b0 == a1 and b0 > 0
+    assert next(o for o in outs if "rank1" in o)["rank1"] is None
