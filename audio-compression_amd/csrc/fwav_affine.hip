@@ -403,7 +403,8 @@ __global__ __launch_bounds__(256) void k_tie_check(const float* __restrict__ ran
                                                    const int32_t* __restrict__ cand, int K,
                                                    const float* __restrict__ pool, const float* __restrict__ emb,
                                                    int64_t q_offset, SgemvSplit sp, const int32_t* __restrict__ ties,
-                                                   int exact_sets, int32_t* __restrict__ resolve) {
+                                                   int exact_sets, int32_t* __restrict__ resolve,
+                                                   const float* __restrict__ qemb) {
   const int lane = threadIdx.x & 63;
   const int64_t w = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (w >= ties[0]) return;
@@ -419,7 +420,7 @@ __global__ __launch_bounds__(256) void k_tie_check(const float* __restrict__ ran
     const int32_t ci = has ? cand[(int64_t)row * K + lane] : -1;
     const int32_t di = ci < 0 ? 0 : ci;
     // exact scores (the search's order) → runs of equal scores → run id per position
-    const float* qp = emb + ((int64_t)row + q_offset) * ED;
+    const float* qp = qemb + ((int64_t)row + q_offset) * ED;  // (the query table: emb, or fwav_tie_check_q's)
     const float* dp = emb + (int64_t)di * ED;
     float sc;
     if constexpr (ED == 16)
@@ -555,7 +556,8 @@ int fwav_debug_gather_rows(const float* table, int64_t n_rows, int rs, int64_t n
 static int tie_check_launch(const char* what, const float* ranges, int64_t n_ranges, int rs, const int32_t* cand,
                             int K, const float* pool, int64_t nd, const float* emb, int emb_dim, int64_t q_offset,
                             int blas_threads, const int32_t* ties, int64_t max_ties, int exact_sets, int32_t* resolve,
-                            void* stream) {
+                            void* stream, const float* qemb = nullptr) {
+  if (qemb == nullptr) qemb = emb;  // the queries are the table's own rows (quirk Q1)
   FWAV_CHECK_ARG(ranges && cand && pool && emb && ties && resolve && n_ranges >= 0 && rs >= 1 && K >= 1 && nd >= 1 &&
                      nd < (int64_t)0x7fffffff && max_ties >= 0 && blas_threads >= 1 && blas_threads <= 4096,
                  FWAV_ERR_ARG, "%s: bad args", what);
@@ -566,7 +568,8 @@ static int tie_check_launch(const char* what, const float* ranges, int64_t n_ran
   const SgemvSplit sp = make_sgemv_split_dim(nd, blas_threads, emb_dim);
   const int64_t grid = cdiv(max_ties, 4);
 #define FWAV_TIE(RSV, EDV)                                                                                         \
-  k_tie_check<RSV, EDV><<<grid, 256, 0, st>>>(ranges, rs, cand, K, pool, emb, q_offset, sp, ties, exact_sets, resolve)
+  k_tie_check<RSV, EDV><<<grid, 256, 0, st>>>(ranges, rs, cand, K, pool, emb, q_offset, sp, ties, exact_sets, resolve, \
+                                              qemb)
   if (emb_dim == 32) {
     switch (rs) {
       case 4: FWAV_TIE(4, 32); break;
@@ -592,6 +595,15 @@ int fwav_tie_check(const float* ranges, int64_t n_ranges, int rs, const int32_t*
                    int64_t max_ties, int exact_sets, int32_t* resolve, void* stream) {
   return tie_check_launch("fwav_tie_check", ranges, n_ranges, rs, cand, K, pool, nd, emb, 16, q_offset, blas_threads,
                           ties, max_ties, exact_sets, resolve, stream);
+}
+
+// fwav_tie_check for a search whose queries were rows of qemb (fwav_sim_topk_q)
+int fwav_tie_check_q(const float* ranges, int64_t n_ranges, int rs, const int32_t* cand, int K, const float* pool,
+                     int64_t nd, const float* emb, const float* qemb, int64_t q_offset, int blas_threads,
+                     const int32_t* ties, int64_t max_ties, int exact_sets, int32_t* resolve, void* stream) {
+  FWAV_CHECK_ARG(qemb && q_offset >= 0, FWAV_ERR_ARG, "fwav_tie_check_q: bad args");
+  return tie_check_launch("fwav_tie_check_q", ranges, n_ranges, rs, cand, K, pool, nd, emb, 16, q_offset, blas_threads,
+                          ties, max_ties, exact_sets, resolve, stream, qemb);
 }
 
 int fwav_tie_check_dim(const float* ranges, int64_t n_ranges, int rs, const int32_t* cand, int K, const float* pool,

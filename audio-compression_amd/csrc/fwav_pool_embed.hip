@@ -587,6 +587,40 @@ static PoolSrc pool_stage(const float* sig, int64_t nd, int rs, int step, int bl
   return PoolSrc{pool, rs, 1, nullptr};
 }
 
+// The embedding stage of fwav_pool_embed and fwav_embed_rows (emb_dim 16): the two-part fp16 table's padded tail
+// zeroed, then k_embed on nd rows read as src[d·a + k·b] — pool rows from pool_stage, or a caller's rows (a = rs,
+// b = 1, no pool_out).
+static void zero_emb16_tail(_Float16* e16, int64_t nd, hipStream_t st) {
+  if (e16 == nullptr || (nd & 255) == 0) return;
+  // the padded tail of the last chunk (both halves of both tables)
+  const int64_t c = nd >> 8, j0 = nd & 255;
+  const int64_t n16 = ((nd + 255) >> 8) * 256 * 16;
+  for (int tb = 0; tb < 2; ++tb)
+    for (int hh = 0; hh < 2; ++hh)
+      (void)hipMemsetAsync(e16 + tb * n16 + ((c * 2 + hh) * 256 + j0) * 8, 0,
+                           (size_t)(256 - j0) * 8 * sizeof(_Float16), st);
+}
+static void embed_stage(const float* src, int64_t nd, int rs, int64_t a, int64_t b, const double* tab, float* pool_out,
+                        float* emb, _Float16* e16, hipStream_t st) {
+  zero_emb16_tail(e16, nd, st);
+  switch (rs) {
+    case 4: launch_embed<4>(src, nd, rs, a, b, tab, pool_out, emb, e16, st); break;
+    case 8: launch_embed<8>(src, nd, rs, a, b, tab, pool_out, emb, e16, st); break;
+    case 16: launch_embed<16>(src, nd, rs, a, b, tab, pool_out, emb, e16, st); break;
+    default: launch_embed<0>(src, nd, rs, a, b, tab, pool_out, emb, e16, st); break;
+  }
+}
+// ... and of fwav_pool_embed_exact and fwav_embed_rows_exact (k_embed_exact, range sizes with a pocketfft plan)
+static void embed_stage_exact(const float* src, int64_t nd, int rs, int64_t a, int64_t b, const double* tab,
+                              const DctPlan& plan, float* pool_out, float* emb, _Float16* e16, hipStream_t st) {
+  zero_emb16_tail(e16, nd, st);
+  if (rs <= 16) launch_embed_exact<16>(src, nd, a, b, tab, plan, pool_out, emb, e16, st);
+  else if (rs <= 24) launch_embed_exact<24>(src, nd, a, b, tab, plan, pool_out, emb, e16, st);
+  else if (rs <= 32) launch_embed_exact<32>(src, nd, a, b, tab, plan, pool_out, emb, e16, st);
+  else if (rs <= 48) launch_embed_exact<48>(src, nd, a, b, tab, plan, pool_out, emb, e16, st);
+  else launch_embed_exact<64>(src, nd, a, b, tab, plan, pool_out, emb, e16, st);
+}
+
 // Domain-embedding rows (emb_dim = 16·NS) → the wide search's fp16 table (store_embh).
 template <int NS>
 __global__ __launch_bounds__(kPoolThreads) void k_embh(const float* __restrict__ emb, int64_t nd,
@@ -753,14 +787,7 @@ int fwav_emb16_from_emb(const float* emb, int64_t nd, void* emb16, void* stream)
   FWAV_CHECK_ARG(emb && emb16 && nd > 0, FWAV_ERR_ARG, "fwav_emb16_from_emb: bad args");
   hipStream_t st = (hipStream_t)stream;
   _Float16* e16 = (_Float16*)emb16;
-  if ((nd & 255) != 0) {
-    const int64_t c = nd >> 8, j0 = nd & 255;
-    const int64_t n16 = ((nd + 255) >> 8) * 256 * 16;
-    for (int tb = 0; tb < 2; ++tb)
-      for (int hh = 0; hh < 2; ++hh)
-        (void)hipMemsetAsync(e16 + tb * n16 + ((c * 2 + hh) * 256 + j0) * 8, 0,
-                             (size_t)(256 - j0) * 8 * sizeof(_Float16), st);
-  }
+  zero_emb16_tail(e16, nd, st);
   k_emb16<<<cdiv(nd, kPoolThreads), kPoolThreads, 0, st>>>(emb, nd, e16);
   FWAV_LAUNCH_CHECK("fwav_emb16_from_emb");
   return FWAV_OK;
@@ -782,22 +809,7 @@ int fwav_pool_embed(const float* sig, int64_t n, int tile, int rs, int step, con
   const float* src = ps.src;
   const int64_t a = ps.a, b = ps.b;
   float* pool_out = ps.pool_out;
-  _Float16* e16 = (_Float16*)emb16;
-  if (e16 != nullptr && (nd & 255) != 0) {
-    // zero the padded tail of the last chunk (both halves of both tables)
-    const int64_t c = nd >> 8, j0 = nd & 255;
-    const int64_t n16 = ((nd + 255) >> 8) * 256 * 16;
-    for (int tb = 0; tb < 2; ++tb)
-      for (int hh = 0; hh < 2; ++hh)
-        (void)hipMemsetAsync(e16 + tb * n16 + ((c * 2 + hh) * 256 + j0) * 8, 0,
-                             (size_t)(256 - j0) * 8 * sizeof(_Float16), st);
-  }
-  switch (rs) {
-    case 4: launch_embed<4>(src, nd, rs, a, b, tab, pool_out, emb, e16, st); break;
-    case 8: launch_embed<8>(src, nd, rs, a, b, tab, pool_out, emb, e16, st); break;
-    case 16: launch_embed<16>(src, nd, rs, a, b, tab, pool_out, emb, e16, st); break;
-    default: launch_embed<0>(src, nd, rs, a, b, tab, pool_out, emb, e16, st); break;
-  }
+  embed_stage(src, nd, rs, a, b, tab, pool_out, emb, (_Float16*)emb16, st);
   FWAV_LAUNCH_CHECK("fwav_pool_embed");
   return FWAV_OK;
 }
@@ -824,22 +836,33 @@ int fwav_pool_embed_exact(const float* sig, int64_t n, int tile, int rs, int ste
   const float* src = ps.src;
   const int64_t a = ps.a, b = ps.b;
   float* pool_out = ps.pool_out;
-  _Float16* e16 = (_Float16*)emb16;
-  if (e16 != nullptr && (nd & 255) != 0) {
-    // zero the padded tail of the last chunk (both halves of both tables)
-    const int64_t c = nd >> 8, j0 = nd & 255;
-    const int64_t n16 = ((nd + 255) >> 8) * 256 * 16;
-    for (int tb = 0; tb < 2; ++tb)
-      for (int hh = 0; hh < 2; ++hh)
-        (void)hipMemsetAsync(e16 + tb * n16 + ((c * 2 + hh) * 256 + j0) * 8, 0,
-                             (size_t)(256 - j0) * 8 * sizeof(_Float16), st);
-  }
-  if (rs <= 16) launch_embed_exact<16>(src, nd, a, b, tab, plan, pool_out, emb, e16, st);
-  else if (rs <= 24) launch_embed_exact<24>(src, nd, a, b, tab, plan, pool_out, emb, e16, st);
-  else if (rs <= 32) launch_embed_exact<32>(src, nd, a, b, tab, plan, pool_out, emb, e16, st);
-  else if (rs <= 48) launch_embed_exact<48>(src, nd, a, b, tab, plan, pool_out, emb, e16, st);
-  else launch_embed_exact<64>(src, nd, a, b, tab, plan, pool_out, emb, e16, st);
+  embed_stage_exact(src, nd, rs, a, b, tab, plan, pool_out, emb, (_Float16*)emb16, st);
   FWAV_LAUNCH_CHECK("fwav_pool_embed_exact");
+  return FWAV_OK;
+}
+
+// ---- embeddings of caller rows (compress_audio(query="range"): the ranges' own embeddings, fractal.py:337-351)
+// fwav_pool_embed's embedding half on n rows of rs floats: the same kernel (k_embed) reading rows[d·rs + k].
+int fwav_embed_rows(const float* rows, int64_t n, int rs, const double* tab, float* emb, void* emb16, void* stream) {
+  FWAV_CHECK_ARG(rows && emb && tab && n >= 0 && rs >= 1, FWAV_ERR_ARG, "fwav_embed_rows: bad args");
+  FWAV_CHECK_ARG(rs <= kMaxPairwise, FWAV_ERR_SHAPE, "fwav_embed_rows: range size out of range");
+  if (n == 0) return FWAV_OK;
+  embed_stage(rows, n, rs, rs, 1, tab, nullptr, emb, (_Float16*)emb16, (hipStream_t)stream);
+  FWAV_LAUNCH_CHECK("fwav_embed_rows");
+  return FWAV_OK;
+}
+
+// fwav_pool_embed_exact's embedding half on n rows of rs floats (k_embed_exact; rs = 4, 8, 16: fwav_embed_rows).
+int fwav_embed_rows_exact(const float* rows, int64_t n, int rs, const double* tab, float* emb, void* emb16,
+                          void* stream) {
+  if (exact_routes_fixed(rs)) return fwav_embed_rows(rows, n, rs, tab, emb, emb16, stream);
+  FWAV_CHECK_ARG(rows && emb && tab && n >= 0 && rs >= 1, FWAV_ERR_ARG, "fwav_embed_rows_exact: bad args");
+  DctPlan plan;
+  FWAV_CHECK_ARG(dct_plan_build(rs, plan), FWAV_ERR_ARG,
+                 "fwav_embed_rows_exact: range size %d has no exact pocketfft plan (fwav_embed_exact_supported)", rs);
+  if (n == 0) return FWAV_OK;
+  embed_stage_exact(rows, n, rs, rs, 1, tab, plan, nullptr, emb, (_Float16*)emb16, (hipStream_t)stream);
+  FWAV_LAUNCH_CHECK("fwav_embed_rows_exact");
   return FWAV_OK;
 }
 

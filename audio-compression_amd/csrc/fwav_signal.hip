@@ -297,6 +297,7 @@ __global__ void k_prune(const float* __restrict__ ranges, int64_t nr, int64_t q_
                         int fast_mode, const float* __restrict__ emb, int64_t nd, int k,
                         const int32_t* __restrict__ zero_cand, int32_t* __restrict__ cand,
                         int32_t* __restrict__ active, int32_t* __restrict__ n_active) {
+  // (emb: the table the query rows are read from — the domain table, quirk Q1, or fwav_prune_q's query table)
   int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= nr) return;
   const int rs = RS > 0 ? RS : rs_rt;
@@ -431,12 +432,14 @@ int fwav_weighted_energy(const float* ranges, int64_t n, float* sum, void* works
 }
 
 // prune_dim: emb rows of emb_dim columns (16: fwav_prune; 32: fwav_prune_dim).
+// emb: the table of n_rows rows the queries are read from (the domain table of nd = n_rows rows, or a query table)
 static int prune_launch(const char* what, const float* ranges, int64_t nr, int64_t q_offset, int rs, float prune_thr,
-                        int fast_mode, const float* emb, int64_t nd, int emb_dim, int k, const int32_t* zero_cand,
-                        int32_t* cand, int32_t* active, int32_t* n_active, void* stream) {
+                        int fast_mode, const float* emb, int64_t n_rows, int64_t nd, int emb_dim, int k,
+                        const int32_t* zero_cand, int32_t* cand, int32_t* active, int32_t* n_active, void* stream) {
   FWAV_CHECK_ARG(ranges && emb && cand && active && n_active && k > 0, FWAV_ERR_ARG, "%s: bad args", what);
-  FWAV_CHECK_ARG(q_offset >= 0 && q_offset + nr <= nd, FWAV_ERR_SHAPE,
-                 "%s: query rows past n_domains (query rows are domain rows, quirk Q1)", what);
+  FWAV_CHECK_ARG(q_offset >= 0 && q_offset + nr <= n_rows, FWAV_ERR_SHAPE,
+                 "%s: query rows past the table's (query rows are domain rows, quirk Q1, unless the call names a "
+                 "query table)", what);
   FWAV_CHECK_ARG(rs <= kMaxPairwise, FWAV_ERR_SHAPE, "%s: rs too large", what);
   hipStream_t st = (hipStream_t)stream;
   (void)hipMemsetAsync(n_active, 0, sizeof(int32_t), st);
@@ -470,15 +473,25 @@ static int prune_launch(const char* what, const float* ranges, int64_t nr, int64
 int fwav_prune(const float* ranges, int64_t nr, int64_t q_offset, int rs, float prune_thr, int fast_mode,
                const float* emb, int64_t nd, int k, const int32_t* zero_cand, int32_t* cand, int32_t* active,
                int32_t* n_active, void* stream) {
-  return prune_launch("fwav_prune", ranges, nr, q_offset, rs, prune_thr, fast_mode, emb, nd, 16, k, zero_cand, cand,
+  return prune_launch("fwav_prune", ranges, nr, q_offset, rs, prune_thr, fast_mode, emb, nd, nd, 16, k, zero_cand, cand,
                       active, n_active, stream);
+}
+
+// fwav_prune with the query of local range i read from row q_offset + i of qemb (n_query_rows rows) instead of the
+// domain table: the same kernel on another table.  n_domains only pads a zero query's row when zero_cand is NULL.
+int fwav_prune_q(const float* ranges, int64_t nr, int64_t q_offset, int rs, float prune_thr, int fast_mode,
+                 const float* qemb, int64_t n_query_rows, int64_t nd, int k, const int32_t* zero_cand, int32_t* cand,
+                 int32_t* active, int32_t* n_active, void* stream) {
+  FWAV_CHECK_ARG(nd > 0, FWAV_ERR_ARG, "fwav_prune_q: no domains");
+  return prune_launch("fwav_prune_q", ranges, nr, q_offset, rs, prune_thr, fast_mode, qemb, n_query_rows, nd, 16, k,
+                      zero_cand, cand, active, n_active, stream);
 }
 
 int fwav_prune_dim(const float* ranges, int64_t nr, int64_t q_offset, int rs, float prune_thr, int fast_mode,
                    const float* emb, int64_t nd, int emb_dim, int k, const int32_t* zero_cand, int32_t* cand,
                    int32_t* active, int32_t* n_active, void* stream) {
   FWAV_CHECK_ARG(emb_dim == 32, FWAV_ERR_ARG, "fwav_prune_dim: emb_dim %d (only 32 is supported)", emb_dim);
-  return prune_launch("fwav_prune_dim", ranges, nr, q_offset, rs, prune_thr, fast_mode, emb, nd, emb_dim, k,
+  return prune_launch("fwav_prune_dim", ranges, nr, q_offset, rs, prune_thr, fast_mode, emb, nd, nd, emb_dim, k,
                       zero_cand, cand, active, n_active, stream);
 }
 

@@ -134,6 +134,16 @@ constexpr int kPlanMaxPieces = 8;
 // ... and any plan's, the floor's later passes included (k_merge_pieces is instantiated for ≤ 8, 16 and 32 pieces)
 constexpr int kMaxPieces = 64;
 static_assert(kPlanMaxPieces <= kMaxPieces, "first-pass plans stay within the merge's widest instantiation");
+// A query table of the search's own (the _q entry points; compress_audio(query="range")): local query i reads row
+// q_offset + i of emb (f32, 16 columns) and of its tiled fp16 high and low parts, and the first pass seeds its band
+// limit from the table rows around min(row·seed_stride, n_domains − 1).  The plain entry points search with the domain
+// table's own rows (quirk Q1) and pass an empty one, which their kernels (XQ = false) never read.
+struct QueryTab {
+  const float* emb = nullptr;
+  const _Float16* hi = nullptr;
+  const _Float16* lo = nullptr;
+  int seed_stride = 1;
+};
 
 #include "fwav_topk_f32.h"
 #include "fwav_topk_plan.h"
@@ -538,11 +548,13 @@ static size_t topk_lds_bytes() {
   return (size_t)kTopkQ * C * sizeof(uint64_t) + 16 * kChunk * sizeof(float) + 3 * kTopkQ * sizeof(int);
 }
 
-template <int C>
+// XQ: the queries are rows of the table xq (the _q entry points), not of emb / emb16
+template <int C, bool XQ = false>
 static int launch_topk(const float* emb, const _Float16* emb16, int64_t nd, const int32_t* active,
                        const int32_t* n_active, int64_t max_q, int64_t q_offset, int K, int32_t* cand, hipStream_t st,
                        uint64_t* gkeys, SgemvSplit sp, int32_t* ties, int dbg = 0,
-                       unsigned long long* stats = nullptr) {
+                       unsigned long long* stats = nullptr, QueryTab xq = QueryTab{}) {
+  const float* const qemb = XQ ? xq.emb : emb;
   const int64_t grid = cdiv(max_q, kTopkQ);
   if (ties != nullptr) (void)hipMemsetAsync(ties, 0, sizeof(int32_t), st);
   if (grid == 0) return FWAV_OK;
@@ -604,9 +616,9 @@ static int launch_topk(const float* emb, const _Float16* emb16, int64_t nd, cons
         constexpr int MODE = decltype(mt)::value;
         auto search = [&](auto counters) {
           constexpr bool STATS = decltype(counters)::value;
-          k_sim_topk_f16<k16Cap, STATS, MODE, ge.W, ge.G, ge.QS, ge.cent><<<pl.items(), 64 * ge.W, 0, st>>>(
+          k_sim_topk_f16<k16Cap, STATS, MODE, ge.W, ge.G, ge.QS, ge.cent, XQ><<<pl.items(), 64 * ge.W, 0, st>>>(
               emb16, emb, nd, act, nact, q_offset, K, cand, gkeys, ovf1, n_ovf1, share, nullptr, 0.0f, rt, P,
-              STATS ? dbg & 65535 : 0, STATS ? stats : nullptr, sp, ties, fl);
+              STATS ? dbg & 65535 : 0, STATS ? stats : nullptr, sp, ties, fl, xq);
         };
         bool counted = false;
 #ifdef FWAV_DEBUG_API
@@ -622,7 +634,7 @@ static int launch_topk(const float* emb, const _Float16* emb16, int64_t nd, cons
           auto merge = [&](auto mp) {
             constexpr int QB = ge.qb();
             k_merge_pieces<k16Cap, QB, MODE == kModeHL, decltype(mp)::value><<<cdiv(pl.R * QB, 4), 256, 0, st>>>(
-                gkeys, act, nact, rt, P, K, cand, ovf1, n_ovf1, share, emb, q_offset, sp, ties, fl);
+                gkeys, act, nact, rt, P, K, cand, ovf1, n_ovf1, share, emb, q_offset, sp, ties, fl, qemb);
           };
           if (pl.P <= 8) merge(std::integral_constant<int, 8>{});
           else if (pl.P <= 16) merge(std::integral_constant<int, 16>{});
@@ -663,7 +675,8 @@ static int launch_topk(const float* emb, const _Float16* emb16, int64_t nd, cons
       } else {
         const int j = K < kFloorJ ? K : kFloorJ, stride = K / j;
         float* est = pilot + (size_t)kFloorPilots * kFloorSlices * kFloorJ;
-        k_floor_pilot<<<kPilotGroups * kFloorSlices, 256, 0, st>>>(emb, nd, order, n_order, q_offset, stride, pilot);
+        k_floor_pilot<<<kPilotGroups * kFloorSlices, 256, 0, st>>>(emb, nd, order, n_order, q_offset, stride, pilot,
+                                                                   qemb);
         k_floor_est<<<kFloorPilots, 64, 0, st>>>(pilot, kFloorSlices, j, est);
         k_floor_reduce<<<1, kFloorPilots, 0, st>>>(est, g_floor_rank, n_order, fmode == 2 ? 0 : (int)kFloorMinQ,
                                                    g_floor2_margin, floor_key);
@@ -688,23 +701,23 @@ static int launch_topk(const float* emb, const _Float16* emb16, int64_t nd, cons
     const int32_t* ex_n = n_ovf1;
     const uint32_t* ex_seeds = seeds1;
     if (mode1 == kModeS16) {
-      k_sim_topk_f16<k16Cap, false, kModeHL><<<pl_re.items(), 64 * k16Waves, 0, st>>>(
+      k_sim_topk_f16<k16Cap, false, kModeHL, k16Waves, kGroup, k16Sets, false, XQ><<<pl_re.items(), 64 * k16Waves, 0, st>>>(
           emb16, emb, nd, ovf1, n_ovf1, q_offset, K, cand, gkeys, ovf2, n_ovf2, nullptr, seeds1, kStreamMargin, 0, 1, 0,
-          nullptr, sp, ties, FloorCtl{nullptr, nullptr, nullptr});
+          nullptr, sp, ties, FloorCtl{nullptr, nullptr, nullptr}, xq);
       ex_in = ovf2;
       ex_n = n_ovf2;
       ex_seeds = seeds2;
     }
 #ifdef FWAV_DEBUG_API
     if (stats != nullptr && (dbg & (1 << 17)))  // diagnostic: counters of the exact-mode relaunch only
-      k_sim_topk_f16<k16Cap, true, kModeEX><<<pl_re.items(), 64 * k16Waves, 0, st>>>(
+      k_sim_topk_f16<k16Cap, true, kModeEX, k16Waves, kGroup, k16Sets, false, XQ><<<pl_re.items(), 64 * k16Waves, 0, st>>>(
           emb16, emb, nd, ex_in, ex_n, q_offset, K, cand, gkeys, ovf2, n_ovf2, nullptr, ex_seeds, kStreamMargin, 0, 1, 0,
-          stats, sp, ties, FloorCtl{nullptr, nullptr, nullptr});
+          stats, sp, ties, FloorCtl{nullptr, nullptr, nullptr}, xq);
     else
 #endif
-      k_sim_topk_f16<k16Cap, false, kModeEX><<<pl_re.items(), 64 * k16Waves, 0, st>>>(
+      k_sim_topk_f16<k16Cap, false, kModeEX, k16Waves, kGroup, k16Sets, false, XQ><<<pl_re.items(), 64 * k16Waves, 0, st>>>(
           emb16, emb, nd, ex_in, ex_n, q_offset, K, cand, gkeys, ovf2, n_ovf2, nullptr, ex_seeds, kStreamMargin, 0, 1, 0,
-          nullptr, sp, ties, FloorCtl{nullptr, nullptr, nullptr});
+          nullptr, sp, ties, FloorCtl{nullptr, nullptr, nullptr}, xq);
   } else {
     const size_t lds = topk_lds_bytes<C>();
     static bool attr32[kMaxDev] = {false};  // a function attribute is set per device
@@ -713,7 +726,7 @@ static int launch_topk(const float* emb, const _Float16* emb16, int64_t nd, cons
       (void)hipFuncSetAttribute((const void*)k_sim_topk_f32<C>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       attr32[dev] = true;
     }
-    k_sim_topk_f32<C><<<grid, kTopkThreads, lds, st>>>(emb, nd, active, n_active, q_offset, K, cand, sp, ties);
+    k_sim_topk_f32<C><<<grid, kTopkThreads, lds, st>>>(emb, nd, active, n_active, q_offset, K, cand, sp, ties, qemb);
   }
   FWAV_LAUNCH_CHECK("fwav_sim_topk");
   return FWAV_OK;
@@ -725,7 +738,7 @@ size_t large_workspace_bytes(int64_t nd, int64_t max_q);
 int launch_topk_large(const float* emb, int64_t nd, const int32_t* active, const int32_t* n_active, int64_t max_q,
                       int64_t q_offset, int K, int32_t* cand, float* S, SgemvSplit sp, int32_t* ties, hipStream_t st);
 int launch_score_rows(const float* emb, int64_t nd, const int32_t* rows, int64_t n_rows, int64_t q_offset,
-                      SgemvSplit sp, float* S, hipStream_t st);
+                      SgemvSplit sp, float* S, hipStream_t st, const float* qemb);  // (qemb NULL: the rows of emb)
 
 }  // namespace fwav
 
@@ -783,7 +796,56 @@ int fwav_score_rows(const float* emb, int64_t nd, const int32_t* rows, int64_t n
   FWAV_CHECK_ARG(blas_threads >= 1 && blas_threads <= 4096, FWAV_ERR_ARG, "fwav_score_rows: blas_threads outside [1, 4096]");
   if (n_rows == 0) return FWAV_OK;
   return launch_score_rows(emb, nd, rows, n_rows, q_offset, make_sgemv_split(nd, blas_threads), scores,
-                           (hipStream_t)stream);
+                           (hipStream_t)stream, nullptr);
+}
+
+// ---- the search with a query table of its own (include/fwav.h, "queries from another table")
+// The shared argument checks of fwav_sim_topk_q and fwav_debug_sim_topk_q (host only), and the kernels' QueryTab.
+static int query_tab(const char* what, const float* emb, const void* emb16, int64_t nd, const float* qemb,
+                     const void* qemb16, int64_t n_query_rows, int seed_stride, int64_t max_q, int64_t q_offset, int K,
+                     QueryTab& xq) {
+  FWAV_CHECK_ARG(emb && qemb && nd > 0 && max_q >= 0, FWAV_ERR_ARG, "%s: bad args", what);
+  FWAV_CHECK_ARG((emb16 == nullptr) == (qemb16 == nullptr), FWAV_ERR_ARG,
+                 "%s: emb16 and qemb16 go together (both for the fp16 search, neither for the all-f32 one)", what);
+  FWAV_CHECK_ARG(n_query_rows > 0 && n_query_rows < (int64_t)0x7fffffff && q_offset >= 0 && q_offset < n_query_rows,
+                 FWAV_ERR_SHAPE, "%s: q_offset %lld outside the %lld query rows", what, (long long)q_offset,
+                 (long long)n_query_rows);
+  FWAV_CHECK_ARG(seed_stride >= 0, FWAV_ERR_ARG, "%s: negative seed_stride", what);
+  FWAV_CHECK_ARG(K >= 1 && K <= 64, FWAV_ERR_K, "%s: K=%d outside [1, 64]", what, K);
+  FWAV_CHECK_ARG(nd < (int64_t)0x7fffffff, FWAV_ERR_SHAPE, "%s: nd too large", what);
+  const _Float16* q16 = (const _Float16*)qemb16;
+  // (the tiled table's low parts follow its high parts: ceil(n_query_rows / 256)·256·16 halfs each, fwav_emb16_elems)
+  xq = QueryTab{qemb, q16, q16 != nullptr ? q16 + cdiv(n_query_rows, kChunk) * kChunk * 16 : nullptr, seed_stride};
+  return FWAV_OK;
+}
+
+int fwav_sim_topk_q(const float* emb, const void* emb16, int64_t nd, const float* qemb, const void* qemb16,
+                    int64_t n_query_rows, int seed_stride, const int32_t* active, const int32_t* n_active,
+                    int64_t max_q, int64_t q_offset, int K, int blas_threads, int32_t* cand, int32_t* ties,
+                    void* workspace, size_t ws_bytes, void* stream) {
+  QueryTab xq;
+  const int rc = query_tab("fwav_sim_topk_q", emb, emb16, nd, qemb, qemb16, n_query_rows, seed_stride, max_q, q_offset,
+                           K, xq);
+  if (rc != FWAV_OK) return rc;
+  FWAV_CHECK_ARG(active && n_active && cand, FWAV_ERR_ARG, "fwav_sim_topk_q: bad args");
+  FWAV_CHECK_ARG(blas_threads >= 1 && blas_threads <= 4096, FWAV_ERR_ARG,
+                 "fwav_sim_topk_q: blas_threads outside [1, 4096]");
+  FWAV_CHECK_ARG(emb16 == nullptr || (workspace && ws_bytes >= fwav_sim_topk_workspace_size(max_q, nd, K)),
+                 FWAV_ERR_WORKSPACE, "fwav_sim_topk_q: workspace too small");
+  return launch_topk<128, true>(emb, (const _Float16*)emb16, nd, active, n_active, max_q, q_offset, K, cand,
+                                (hipStream_t)stream, (uint64_t*)workspace, make_sgemv_split(nd, blas_threads), ties, 0,
+                                nullptr, xq);
+}
+
+int fwav_score_rows_q(const float* emb, int64_t nd, const float* qemb, const int32_t* rows, int64_t n_rows,
+                      int64_t q_offset, int blas_threads, float* scores, void* stream) {
+  FWAV_CHECK_ARG(emb && qemb && rows && scores && nd > 0 && nd < (int64_t)0x7fffffff && n_rows >= 0 && q_offset >= 0,
+                 FWAV_ERR_ARG, "fwav_score_rows_q: bad args");
+  FWAV_CHECK_ARG(blas_threads >= 1 && blas_threads <= 4096, FWAV_ERR_ARG,
+                 "fwav_score_rows_q: blas_threads outside [1, 4096]");
+  if (n_rows == 0) return FWAV_OK;
+  return launch_score_rows(emb, nd, rows, n_rows, q_offset, make_sgemv_split(nd, blas_threads), scores,
+                           (hipStream_t)stream, qemb);
 }
 
 #ifdef FWAV_DEBUG_API  // ---- debug library only (include/fwav_debug.h)
@@ -798,6 +860,33 @@ int fwav_debug_sim_topk(const float* emb, const void* emb16, int64_t nd, const i
                  "fwav_debug_sim_topk: workspace too small for max_q=%lld", (long long)max_q);
   return launch_topk<128>(emb, (const _Float16*)emb16, nd, active, n_active, max_q, q_offset, K, cand,
                           (hipStream_t)stream, (uint64_t*)workspace, make_sgemv_split(nd, 1), nullptr, dbg, stats);
+}
+
+// fwav_debug_sim_topk with the queries of fwav_sim_topk_q: the forced geometry, mode, floor and plan apply alike.
+int fwav_debug_sim_topk_q(const float* emb, const void* emb16, int64_t nd, const float* qemb, const void* qemb16,
+                          int64_t n_query_rows, int seed_stride, const int32_t* active, const int32_t* n_active,
+                          int64_t max_q, int64_t q_offset, int K, int32_t* cand, void* workspace, size_t ws_bytes,
+                          int dbg, unsigned long long* stats, void* stream) {
+  FWAV_CHECK_ARG(emb16 && qemb16 && workspace && active && n_active && cand, FWAV_ERR_ARG,
+                 "fwav_debug_sim_topk_q: bad args");
+  QueryTab xq;
+  const int rc = query_tab("fwav_debug_sim_topk_q", emb, emb16, nd, qemb, qemb16, n_query_rows, seed_stride, max_q,
+                           q_offset, K, xq);
+  if (rc != FWAV_OK) return rc;
+  FWAV_CHECK_ARG(ws_bytes >= fwav_sim_topk_workspace_size(max_q, nd, K), FWAV_ERR_WORKSPACE,
+                 "fwav_debug_sim_topk_q: workspace too small for max_q=%lld", (long long)max_q);
+  return launch_topk<128, true>(emb, (const _Float16*)emb16, nd, active, n_active, max_q, q_offset, K, cand,
+                                (hipStream_t)stream, (uint64_t*)workspace, make_sgemv_split(nd, 1), nullptr, dbg, stats,
+                                xq);
+}
+
+// The table row at which fwav_sim_topk_q's first pass centres the seed window of query row `row` (the kernels' own
+// seed_centre, on the host): min(row·seed_stride, n_domains − 1).
+int64_t fwav_debug_seed_centre(int64_t row, int seed_stride, int64_t nd) {
+  if (row < 0 || seed_stride < 0 || nd <= 0) return -1;
+  QueryTab xq;
+  xq.seed_stride = seed_stride;
+  return seed_centre<true>(row, xq, nd);
 }
 
 // Diagnostic override of the first pass's mode: 0 = S16 (→ HL → exact relaunches), 1 = HL (→ exact), −1 = by table

@@ -8,7 +8,8 @@ __global__ __launch_bounds__(kTopkThreads) void k_sim_topk_f32(const float* __re
                                                                const int32_t* __restrict__ active,
                                                                const int32_t* __restrict__ n_active_p,
                                                                int64_t q_offset, int K, int32_t* __restrict__ cand,
-                                                               SgemvSplit sp, int32_t* __restrict__ ties) {
+                                                               SgemvSplit sp, int32_t* __restrict__ ties,
+                                                               const float* __restrict__ qemb) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   uint64_t* keys = (uint64_t*)smem;                            // [kTopkQ][C]
   float* lda = (float*)(keys + (size_t)kTopkQ * C);            // [kChunk][16] (row-major domain rows)
@@ -31,9 +32,9 @@ __global__ __launch_bounds__(kTopkThreads) void k_sim_topk_f32(const float* __re
   const int qi = qbase + ql;
   const int32_t q = qi < n_active ? active[qi] : -1;
 
-  float qf[16];  // the whole query vector (sgemv16)
+  float qf[16];  // the whole query vector (sgemv16), a row of the query table (emb itself, or the _q entry point's)
 #pragma unroll
-  for (int k = 0; k < 16; ++k) qf[k] = q >= 0 ? emb[((int64_t)q + q_offset) * 16 + k] : 0.0f;
+  for (int k = 0; k < 16; ++k) qf[k] = q >= 0 ? qemb[((int64_t)q + q_offset) * 16 + k] : 0.0f;
   float th = q >= 0 ? -INFINITY : INFINITY;  // invalid lanes never append
   if (tid < kTopkQ) {
     cnt[tid] = 0;

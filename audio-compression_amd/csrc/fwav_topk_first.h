@@ -210,7 +210,8 @@ __device__ __forceinline__ void compact16_s16(uint64_t* __restrict__ kq, int n0,
 }
 
 // Final pass of query ql (a whole-table item): rescore its two-ended buffer (sm.cnt entries at the front, sm.cnt1 at
-// the back) in exact f32 (sgemv16), sort, emit the top K to `out`; qrow = the query's table row.  Whole wave.  Every
+// the back) in exact f32 (sgemv16), sort, emit the top K to `out`; qrow = the query's row of the query table qemb
+// (the domain table itself unless the search was given another, QueryTab).  Whole wave.  Every
 // per-query buffer and counter is owned by one wave, so no cross-wave fences are needed; the wave's own appended
 // stores are drained once (vmcnt(0)), then all key loads and all row loads are issued together (two memory round
 // trips in total).
@@ -218,12 +219,13 @@ template <int C, int E, class SM>
 __device__ __forceinline__ void compact16_e(uint64_t* __restrict__ kq, SM& sm, int ql, int K,
                                             const float* __restrict__ emb, int32_t* __restrict__ out,
                                             const SgemvSplit& sp, int32_t* __restrict__ ties, int32_t qid,
-                                            uint32_t fkey, const FloorCtl& fl, int64_t qrow) {
+                                            uint32_t fkey, const FloorCtl& fl, const float* __restrict__ qemb,
+                                            int64_t qrow) {
   const int lane = threadIdx.x & 63;
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   const int n0 = sm.cnt[ql];
   const int n = min(n0 + sm.cnt1[ql], C);
-  const float4* qp = reinterpret_cast<const float4*>(emb + qrow * 16);
+  const float4* qp = reinterpret_cast<const float4*>(qemb + qrow * 16);
   uint64_t v[E];
 #pragma unroll
   for (int j = 0; j < E; ++j) {
@@ -289,12 +291,13 @@ template <int C, class SM>
 __device__ __forceinline__ void compact16(uint64_t* __restrict__ kq, SM& sm, int ql, int K,
                                           const float* __restrict__ emb, int32_t* __restrict__ out,
                                           const SgemvSplit& sp, int32_t* __restrict__ ties, int32_t qid,
-                                          uint32_t fkey, const FloorCtl& fl, int64_t qrow) {
+                                          uint32_t fkey, const FloorCtl& fl, const float* __restrict__ qemb,
+                                          int64_t qrow) {
   const int n = __builtin_amdgcn_readfirstlane(sm.cnt[ql] + sm.cnt1[ql]);
   if (C > 128 && n <= 128)
-    compact16_e<C, 2, SM>(kq, sm, ql, K, emb, out, sp, ties, qid, fkey, fl, qrow);
+    compact16_e<C, 2, SM>(kq, sm, ql, K, emb, out, sp, ties, qid, fkey, fl, qemb, qrow);
   else
-    compact16_e<C, C / 64, SM>(kq, sm, ql, K, emb, out, sp, ties, qid, fkey, fl, qrow);
+    compact16_e<C, C / 64, SM>(kq, sm, ql, K, emb, out, sp, ties, qid, fkey, fl, qemb, qrow);
 }
 
 // End of a table piece (split block): no rescoring and no sort here — the piece keeps the entries of its band whose
@@ -653,6 +656,17 @@ __device__ __forceinline__ float replay_window(const _Float16* __restrict__ emb1
 // free: each query's two lanes combine their counts by one shuffle).  Returns −∞ when fewer than K window scores
 // are ≥ 0.
 constexpr int kSeedHalf = 64;
+// The table row a query's seed window is centred at: the query's own row, or with a query table of its own (XQ) row
+// qrow·seed_stride clamped into the table (there may be more query rows than domains).
+template <bool XQ>
+__host__ __device__ __forceinline__ int64_t seed_centre(int64_t qrow, const QueryTab& xq, int64_t nd) {
+  if constexpr (XQ) {
+    const int64_t c = qrow * (int64_t)xq.seed_stride;
+    return c < nd ? c : nd - 1;
+  } else {
+    return qrow;
+  }
+}
 constexpr int kSeedTiles = (2 * kSeedHalf + 62) / 32 + 1;  // the wave's 32 windows from a tile-aligned base
 // LEAN (the 4-set centroid geometry, whose prologue holds 4 sets' fragments): the tiles' addresses as wave-uniform
 // offsets (wbase is uniform) plus one per-lane index, instead of a 64-bit pointer per tile and lane.
@@ -945,7 +959,11 @@ if constexpr (NT <= 32) {
 }
 }
 
-template <int C, bool STATS, int MODE, int W = k16Waves, int G = kGroup, int QS = k16Sets, bool CENT = false>
+// XQ: the queries come from a table of their own (QueryTab xq: the _q entry points) instead of the domain table's
+// rows; everything read from the table — the stream, the seeds' tiles, the rescoring rows — is the same.  A separate
+// instantiation, so that the plain search's code is what it was without the option.
+template <int C, bool STATS, int MODE, int W = k16Waves, int G = kGroup, int QS = k16Sets, bool CENT = false,
+          bool XQ = false>
 __global__ __launch_bounds__(64 * W, MODE == kModeEX ? kExactWavesPerSimd : (CENT ? kCentWavesPerSimd : kWavesPerSimd)) void k_sim_topk_f16(const _Float16* __restrict__ emb16,
                                                                 const float* __restrict__ emb, int64_t nd,
                                                                 const int32_t* __restrict__ active,
@@ -959,7 +977,7 @@ __global__ __launch_bounds__(64 * W, MODE == kModeEX ? kExactWavesPerSimd : (CEN
                                                                 float seed_shift, int plan_rt,
                                                                 int plan_p, int dbg, unsigned long long* gstats,
                                                                 SgemvSplit sp, int32_t* __restrict__ ties,
-                                                                FloorCtl fl) {
+                                                                FloorCtl fl, QueryTab xq) {
   constexpr bool EX = MODE == kModeEX;
   constexpr bool HL = MODE == kModeHL;
   constexpr int NG = W * QS;  // query groups of 32 per workgroup; wave w owns groups w·QS .. w·QS + QS − 1
@@ -1023,6 +1041,10 @@ __global__ __launch_bounds__(64 * W, MODE == kModeEX ? kExactWavesPerSimd : (CEN
   float qv[QS][EX ? 16 : 1];  // EX: the exact query vector (sgemv16 keys)
   const int64_t n16 = (int64_t)cdiv(nd, kChunk) * kChunk * 16;  // halfs per fp16 table
   const _Float16* emb16lo = emb16 + n16;
+  // where the queries are read: their f32 rows and fp16 high and low parts
+  const float* const qemb = XQ ? xq.emb : emb;
+  const _Float16* const q16 = XQ ? xq.hi : emb16;
+  const _Float16* const q16lo = XQ ? xq.lo : emb16lo;
   uint64_t kth[QS];           // EX: the query's current K-th exact key (0 until K entries)
   float inseed[QS];           // relaunch: the previous pass's band limit at overflow, in this mode's scale
   int32_t qpos[QS];           // the slot's query position in the active list
@@ -1038,8 +1060,8 @@ __global__ __launch_bounds__(64 * W, MODE == kModeEX ? kExactWavesPerSimd : (CEN
     const int64_t qrow = (int64_t)(q < 0 ? 0 : q) + q_offset;
     // (COLD loads b[s] with the set's seed, below: the seed of set s runs with s + 1 fragments held, not all QS)
     if constexpr (!COLD)
-      b[s] = *reinterpret_cast<const half8*>(emb16 + (((qrow >> 8) * 2 + h) * 256 + (qrow & 255)) * 8);
-    bl[s] = *reinterpret_cast<const half8*>(emb16lo + (((qrow >> 8) * 2 + h) * 256 + (qrow & 255)) * 8);
+      b[s] = *reinterpret_cast<const half8*>(q16 + (((qrow >> 8) * 2 + h) * 256 + (qrow & 255)) * 8);
+    bl[s] = *reinterpret_cast<const half8*>(q16lo + (((qrow >> 8) * 2 + h) * 256 + (qrow & 255)) * 8);
     upd[s] = (q >= 0 && !(dbg & 1)) ? 1 : 0;
     thf[s] = upd[s] ? -INFINITY : INFINITY;  // slots past n_active never take appends
     qpos[s] = (int32_t)(qi < n_active ? qi : 0);
@@ -1064,13 +1086,14 @@ __global__ __launch_bounds__(64 * W, MODE == kModeEX ? kExactWavesPerSimd : (CEN
     // (COLD reads it where it is applied, below: nothing held through the seeds' MFMAs)
     inseed[s] = !COLD && seeds_in != nullptr && q >= 0 ? key2f(seeds_in[qi]) - seed_shift : -INFINITY;
     if constexpr (EX) {
-      const float* qp = emb + qrow * 16;
+      const float* qp = qemb + qrow * 16;
 #pragma unroll
       for (int i = 0; i < 16; ++i) qv[s][i] = qp[i];
     }
   }
 
-  // seed the band limits from the queries' own domain windows (tiles from the wave's first query row)
+  // seed the band limits from the queries' own domain windows (tiles from the wave's first query row; XQ: from the
+  // window of table rows around seed_centre of the query's row — any K in-table rows give a valid limit)
   if (COLD || !(ABL && (dbg & 8192))) {  // ablation 8192: no seed
 #pragma unroll
     for (int s = 0; s < QS; ++s) {
@@ -1080,13 +1103,14 @@ __global__ __launch_bounds__(64 * W, MODE == kModeEX ? kExactWavesPerSimd : (CEN
       if constexpr (COLD) {  // (read again from the active list: not held through the other sets' seeds)
         const int64_t qi = slot_query(block, qslot0 + (wave * QS + s) * 32 + col, plan.nb);
         const int32_t q = qi < n_active ? active[qi] : -1;
-        qrow_s = (int64_t)(q < 0 ? 0 : q) + q_offset;
+        const int64_t qrow_q = (int64_t)(q < 0 ? 0 : q) + q_offset;
+        qrow_s = seed_centre<XQ>(qrow_q, xq, nd);
         qrow_0 = __builtin_amdgcn_readfirstlane((int)qrow_s);
-        b[s] = *reinterpret_cast<const half8*>(emb16 + (((qrow_s >> 8) * 2 + h) * 256 + (qrow_s & 255)) * 8);
+        b[s] = *reinterpret_cast<const half8*>(q16 + (((qrow_q >> 8) * 2 + h) * 256 + (qrow_q & 255)) * 8);
         if (ABL && (dbg & 8192)) continue;
       } else {
-        qrow_s = sm.qrow[(wave * QS + s) * 32 + col];
-        qrow_0 = __builtin_amdgcn_readfirstlane((int)sm.qrow[(wave * QS + s) * 32]);
+        qrow_s = seed_centre<XQ>(sm.qrow[(wave * QS + s) * 32 + col], xq, nd);
+        qrow_0 = __builtin_amdgcn_readfirstlane((int)seed_centre<XQ>(sm.qrow[(wave * QS + s) * 32], xq, nd));
       }
       const int64_t wbase = (int64_t)((qrow_0 - kSeedHalf) >> 5) << 5;
       const float seed = seed_limit<MODE, COLD>(emb16, nd, b[s], qrow_s, wbase, K);
@@ -1126,7 +1150,7 @@ __global__ __launch_bounds__(64 * W, MODE == kModeEX ? kExactWavesPerSimd : (CEN
 #pragma unroll
     for (int s = 1; s < QS; ++s) ls = sj == s ? lid[s] : ls;
     if constexpr (COLD) ls = wave * QS + sj;  // (the select chain over 4 sets became a table in scratch)
-    centroid_setup<QS>(emb16, [&](int k) -> int64_t {
+    centroid_setup<QS>(q16, [&](int k) -> int64_t {
       const int64_t qi = slot_query(block, qslot0 + ls * 32 + mcol0 + k, plan.nb);
       return qi < n_active ? (int64_t)active[qi] + q_offset : (int64_t)-1;
     }, bc, cb);
@@ -1447,7 +1471,7 @@ __global__ __launch_bounds__(64 * W, MODE == kModeEX ? kExactWavesPerSimd : (CEN
     int64_t qrow;
     if constexpr (COLD) qrow = (int64_t)qid + q_offset;
     else qrow = sm.qrow[qs];
-    compact16<C>(kq, sm, qs, K, emb, cand + (int64_t)qid * K, sp, ties, qid, fkey, fl, qrow);
+    compact16<C>(kq, sm, qs, K, emb, cand + (int64_t)qid * K, sp, ties, qid, fkey, fl, qemb, qrow);
     // overflowed: listed for the exact-mode relaunch with its band limit as the seed (same list position)
     if (lane == 0 && sm.ovf[qs]) {
       const int pos = atomicAdd(n_ovf, 1);

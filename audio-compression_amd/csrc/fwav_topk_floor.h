@@ -47,7 +47,8 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 __global__ __launch_bounds__(256) void k_floor_pilot(const float* __restrict__ emb, int64_t nd,
                                                      const int32_t* __restrict__ active,
                                                      const int32_t* __restrict__ n_active_p, int64_t q_offset,
-                                                     int stride, float* __restrict__ scratch) {
+                                                     int stride, float* __restrict__ scratch,
+                                                     const float* __restrict__ qemb) {
   __shared__ float4 rows[256][4];
   __shared__ float lists[4][64][kFloorJ + 1];
   const int na = *n_active_p;
@@ -60,7 +61,7 @@ __global__ __launch_bounds__(256) void k_floor_pilot(const float* __restrict__ e
   {
     const int64_t pos = na > 0 ? (int64_t)p * na / kFloorPilots : 0;
     const int64_t row = na > 0 ? (int64_t)active[pos] + q_offset : 0;
-    const float4* qp = reinterpret_cast<const float4*>(emb + row * 16);
+    const float4* qp = reinterpret_cast<const float4*>(qemb + row * 16);  // (the query table: emb itself, or the _q one)
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const float4 v = qp[k];

@@ -74,11 +74,13 @@ __global__ __launch_bounds__(kScoreThreads) void k_scores_batch(const float* __r
   }
 }
 
-// S[i·nd + d] = score(domain d, query row q_offset + rows[i]), i < n_rows (fwav_score_rows).
+// S[i·nd + d] = score(domain d, query row q_offset + rows[i]), i < n_rows (fwav_score_rows); the query rows are rows of
+// qemb (emb itself, or fwav_score_rows_q's query table).
 template <int ED>
 __global__ __launch_bounds__(kScoreThreads) void k_score_rows(const float* __restrict__ emb, int64_t nd,
                                                               const int32_t* __restrict__ rows, int n_rows,
-                                                              int64_t q_offset, SgemvSplit sp, float* __restrict__ S) {
+                                                              int64_t q_offset, SgemvSplit sp, float* __restrict__ S,
+                                                              const float* __restrict__ qemb) {
   __shared__ float qv[kScoreQ][ED];
   const int64_t d = (int64_t)blockIdx.x * kScoreThreads + threadIdx.x;
   float e[ED];
@@ -89,7 +91,7 @@ __global__ __launch_bounds__(kScoreThreads) void k_score_rows(const float* __res
     __syncthreads();
     for (int t = threadIdx.x; t < m * ED; t += kScoreThreads) {
       const int64_t q = (int64_t)rows[j0 + t / ED] + q_offset;
-      qv[t / ED][t % ED] = emb[q * ED + t % ED];
+      qv[t / ED][t % ED] = qemb[q * ED + t % ED];
     }
     __syncthreads();
     if (d < nd)
@@ -333,23 +335,24 @@ int launch_topk_large(const float* emb, int64_t nd, const int32_t* active, const
 }
 
 int launch_score_rows_dim(const float* emb, int64_t nd, int dim, const int32_t* rows, int64_t n_rows, int64_t q_offset,
-                          SgemvSplit sp, float* S, hipStream_t st) {
+                          SgemvSplit sp, float* S, hipStream_t st, const float* qemb) {
+  if (qemb == nullptr) qemb = emb;
   for (int64_t r0 = 0; r0 < n_rows; r0 += 4096) {
     const int m = (int)std::min<int64_t>(4096, n_rows - r0);
     if (dim == 32)
       k_score_rows<32><<<cdiv(nd, kScoreThreads), kScoreThreads, 0, st>>>(emb, nd, rows + r0, m, q_offset, sp,
-                                                                           S + r0 * nd);
+                                                                           S + r0 * nd, qemb);
     else
       k_score_rows<16><<<cdiv(nd, kScoreThreads), kScoreThreads, 0, st>>>(emb, nd, rows + r0, m, q_offset, sp,
-                                                                           S + r0 * nd);
+                                                                           S + r0 * nd, qemb);
   }
   FWAV_LAUNCH_CHECK("fwav_score_rows");
   return FWAV_OK;
 }
 
 int launch_score_rows(const float* emb, int64_t nd, const int32_t* rows, int64_t n_rows, int64_t q_offset,
-                      SgemvSplit sp, float* S, hipStream_t st) {
-  return launch_score_rows_dim(emb, nd, 16, rows, n_rows, q_offset, sp, S, st);
+                      SgemvSplit sp, float* S, hipStream_t st, const float* qemb) {
+  return launch_score_rows_dim(emb, nd, 16, rows, n_rows, q_offset, sp, S, st, qemb);
 }
 
 }  // namespace fwav

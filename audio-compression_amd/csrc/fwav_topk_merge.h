@@ -14,7 +14,7 @@
 // (score desc, index asc), listed if tied, the first K emitted.
 template <int E>
 __device__ __forceinline__ void merge_band(const uint64_t* __restrict__ sw, int mb, int K, const float* __restrict__ emb,
-                                           int64_t qrow, const SgemvSplit& sp, int32_t* __restrict__ ties, int32_t qid,
+                                           const float* __restrict__ qemb, int64_t qrow, const SgemvSplit& sp, int32_t* __restrict__ ties, int32_t qid,
                                            int32_t* __restrict__ out, uint32_t fkey, const FloorCtl& fl) {
   const int lane = threadIdx.x & 63;
   uint64_t v[E];
@@ -23,7 +23,7 @@ __device__ __forceinline__ void merge_band(const uint64_t* __restrict__ sw, int 
     const int e = j * 64 + lane;
     v[j] = e < mb ? sw[e] : 0ull;
   }
-  const float4* qp = reinterpret_cast<const float4*>(emb + qrow * 16);
+  const float4* qp = reinterpret_cast<const float4*>(qemb + qrow * 16);  // qrow: a row of the query table
   float qv[16];
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -78,7 +78,7 @@ __device__ __forceinline__ void merge_query(const TopkPlan& plan, int64_t w, int
                                             int32_t* __restrict__ ovf_list, int32_t* __restrict__ n_ovf,
                                             const uint32_t* __restrict__ share, const float* __restrict__ emb,
                                             int64_t q_offset, const SgemvSplit& sp, int32_t* __restrict__ ties,
-                                            uint32_t fkey, const FloorCtl& fl);
+                                            uint32_t fkey, const FloorCtl& fl, const float* __restrict__ qemb);
 
 // k_merge_pieces' union: the pieces' bands hold n = Σ counts entries (cfg2: mean 174, max 268 over 60,416 queries;
 // those above the shared limit Lk mean 163; the band kept after the select mean 78, max 113: tools/diag/
@@ -98,7 +98,8 @@ __global__ __launch_bounds__(256) void k_merge_pieces(const uint64_t* __restrict
                                                       int K, int32_t* __restrict__ cand, int32_t* __restrict__ ovf_list,
                                                       int32_t* __restrict__ n_ovf, const uint32_t* __restrict__ share,
                                                       const float* __restrict__ emb, int64_t q_offset, SgemvSplit sp,
-                                                      int32_t* __restrict__ ties, FloorCtl fl) {
+                                                      int32_t* __restrict__ ties, FloorCtl fl,
+                                                      const float* __restrict__ qemb) {
   const int n_active = *n_active_p;
   const uint32_t fkey = fl.key != nullptr ? __builtin_amdgcn_readfirstlane(*fl.key) : 0u;
   const bool alt = fl.key != nullptr && fkey == 0u;  // the floor did not apply: the floor-free plan (FloorCtl)
@@ -116,7 +117,7 @@ __global__ __launch_bounds__(256) void k_merge_pieces(const uint64_t* __restrict
   const int64_t w = (int64_t)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   if (w < plan.R * QB)
     merge_query<C, QB, HL, MP>(plan, w, lane, sw, sh, gkeys_all, active, n_active, K, cand, ovf_list, n_ovf, share,
-                               emb, q_offset, sp, ties, fkey, fl);
+                               emb, q_offset, sp, ties, fkey, fl, qemb);
 }
 
 // One split-block query w of k_merge_pieces (whole wave; sw: the wave's LDS row).
@@ -127,7 +128,7 @@ __device__ __forceinline__ void merge_query(const TopkPlan& plan, int64_t w, int
                                             int32_t* __restrict__ ovf_list, int32_t* __restrict__ n_ovf,
                                             const uint32_t* __restrict__ share, const float* __restrict__ emb,
                                             int64_t q_offset, const SgemvSplit& sp, int32_t* __restrict__ ties,
-                                            uint32_t fkey, const FloorCtl& fl) {
+                                            uint32_t fkey, const FloorCtl& fl, const float* __restrict__ qemb) {
   constexpr int E = C / 64;
   constexpr int kBit0 = HL ? 0 : 12;  // the select's resolution (S16 needs the K-th only at ≈ 2^-11)
   constexpr int kHiRows = merge_hi_rows(MP);
@@ -332,7 +333,7 @@ __device__ __forceinline__ void merge_query(const TopkPlan& plan, int64_t w, int
   }
   // same wave: its own ds_writes are ordered before merge_band's reads
   if (C > 128 && mb <= 128)
-    merge_band<2>(sw, mb, K, emb, (int64_t)qid + q_offset, sp, ties, qid, cand + (int64_t)qid * K, fkey, fl);
+    merge_band<2>(sw, mb, K, emb, qemb, (int64_t)qid + q_offset, sp, ties, qid, cand + (int64_t)qid * K, fkey, fl);
   else
-    merge_band<E>(sw, mb, K, emb, (int64_t)qid + q_offset, sp, ties, qid, cand + (int64_t)qid * K, fkey, fl);
+    merge_band<E>(sw, mb, K, emb, qemb, (int64_t)qid + q_offset, sp, ties, qid, cand + (int64_t)qid * K, fkey, fl);
 }

@@ -51,7 +51,7 @@ int launch_topk_large_dim(const float* emb, int64_t nd, int dim, const int32_t* 
                           int64_t max_q, int64_t q_offset, int K, int32_t* cand, float* S, SgemvSplit sp,
                           int32_t* ties, hipStream_t st);
 int launch_score_rows_dim(const float* emb, int64_t nd, int dim, const int32_t* rows, int64_t n_rows, int64_t q_offset,
-                          SgemvSplit sp, float* S, hipStream_t st);
+                          SgemvSplit sp, float* S, hipStream_t st, const float* qemb);
 
 template <int NS>
 constexpr size_t wide_lds_bytes() {
@@ -269,7 +269,7 @@ int fwav_score_rows_dim(const float* emb, int64_t nd, int emb_dim, const int32_t
                  "fwav_score_rows_dim: blas_threads outside [1, 4096]");
   if (n_rows == 0) return FWAV_OK;
   return launch_score_rows_dim(emb, nd, emb_dim, rows, n_rows, q_offset,
-                               make_sgemv_split_dim(nd, blas_threads, emb_dim), scores, (hipStream_t)stream);
+                               make_sgemv_split_dim(nd, blas_threads, emb_dim), scores, (hipStream_t)stream, nullptr);
 }
 
 // Test hook (host, no device): one (domain row, query row) pair of emb_dim = 32 floats through the search's own

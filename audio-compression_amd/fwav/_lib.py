@@ -58,6 +58,12 @@ SIGNATURES = {
     "fwav_compact_workspace_size": (SZ, [I64, I64]),
     "fwav_compact_domains": (I32, [P, I64, P, I64, I32, P, P, P, P, P, SZ, P]),
     "fwav_emb16_from_emb": (I32, [P, I64, P, P]),
+    "fwav_embed_rows": (I32, [P, I64, I32, P, P, P, P]),
+    "fwav_embed_rows_exact": (I32, [P, I64, I32, P, P, P, P]),
+    "fwav_prune_q": (I32, [P, I64, I64, I32, F32, I32, P, I64, I64, I32, P, P, P, P, P]),
+    "fwav_sim_topk_q": (I32, [P, P, I64, P, P, I64, I32, P, P, I64, I64, I32, I32, P, P, P, SZ, P]),
+    "fwav_score_rows_q": (I32, [P, I64, P, P, I64, I64, I32, P, P]),
+    "fwav_tie_check_q": (I32, [P, I64, I32, P, I32, P, I64, P, P, I64, I32, P, I64, I32, P, P]),
     "fwav_embh_elems": (SZ, [I64, I32]),
     "fwav_embh_from_emb": (I32, [P, I64, I32, P, P]),
     "fwav_embed_tables_dim_size": (SZ, [I32, I32]),
@@ -88,6 +94,8 @@ SIGNATURES = {
 #: diagnostics; libfwav.so exports none of them
 DEBUG_SIGNATURES = {
     "fwav_debug_sim_topk": (I32, [P, P, I64, P, P, I64, I64, I32, P, P, SZ, I32, P, P]),
+    "fwav_debug_sim_topk_q": (I32, [P, P, I64, P, P, I64, I32, P, P, I64, I64, I32, P, P, SZ, I32, P, P]),
+    "fwav_debug_seed_centre": (I64, [I64, I32, I64]),
     "fwav_debug_topk_plan": (I32, [I32, I32]),
     "fwav_debug_topk_tail": (I32, [I32]),
     "fwav_debug_topk_plan_cover": (I32, [I64, I32, I32, I32, P, P]),

@@ -2,11 +2,15 @@
 
   python fractal.py compress IN OUT [--tile 1024] [--energy-thresh 1e-4] [--gpu] [--batch] [--out DIR] [--workers 4]
                             [--embedding {matrix,pocketfft}] [--emb-dim {16,32}]
-                            [--compact]
+                            [--compact] [--query {domain_row,range}]
   python fractal.py decompress IN [--out PATH] [--iter 8] [--eps 1e-3] [--gpu] [--batch] [--workers 4]
+                              [--s-damping 0.0]
   python fractal.py compact IN.fwav [--out PATH]
 
---embedding, --emb-dim, --compact and the compact sub-command are this port's extras.  --compact stores only the
+--embedding, --emb-dim, --compact, --query, --s-damping and the compact sub-command are this port's extras.  --query
+range searches with each range's own embedding instead of the reference pipeline's domain row i (quirk Q1): better
+matches, not the reference's file; they reach the decoded signal through --s-damping d with a small positive d
+(decompress_audio's s_damping, fractal.py:1445; at the reference's 0.0 the decoder uses s = 0).  --compact stores only the
 domain rows that some match names, with the match indices renumbered: a valid version-1 file, a fraction of the size,
 that any decoder of the format reads to the same samples; `compact` re-packs an existing file that way (default output:
 IN with .compact.fwav in place of .fwav).  --emb-dim is compress_audio's emb_dim (the reference's CLI
@@ -95,6 +99,9 @@ def build_parser() -> argparse.ArgumentParser:
                     help="embedding width (compress_audio's emb_dim): two heads of 8 or of 16 DCT coefficients")
     pc.add_argument("--compact", action="store_true",
                     help="store only the domain rows that some match names (a smaller, valid .fwav)")
+    pc.add_argument("--query", choices=("domain_row", "range"), default="domain_row",
+                    help="range i's query vector: domain-embedding row i (the reference's pipeline) or the embedding "
+                         "of the range itself (closer matches; not the reference's file)")
     pk = sub.add_parser("compact")
     pk.add_argument("input", help="input FWAV file")
     pk.add_argument("--out", default=None, help="output FWAV file (default: IN with .compact.fwav for .fwav)")
@@ -103,6 +110,8 @@ def build_parser() -> argparse.ArgumentParser:
     pd.add_argument("--out", default=None, help="output file or directory")
     pd.add_argument("--iter", type=int, default=8)
     pd.add_argument("--eps", type=float, default=1e-3)
+    pd.add_argument("--s-damping", type=float, default=0.0,
+                    help="decompress_audio's s_damping: s = (1 - d) * stored s + d * re-fitted s (default 0.0)")
     pd.add_argument("--gpu", action="store_true")
     pd.add_argument("--batch", action="store_true", help="treat input as directory and decompress all FWAV inside")
     pd.add_argument("--workers", type=int, default=4, help="parallel file-level workers for batch")
@@ -120,7 +129,7 @@ def main(argv=None):
             if args.output is None:
                 parser.error("compress requires OUTPUT unless --batch is used")
             return _compress_job((args.input, args.output, args.tile, args.energy_thresh, args.gpu, args.embedding,
-                                  args.emb_dim, args.compact))
+                                  args.emb_dim, args.compact, args.query))
         if args.output is not None:
             parser.error("Do not provide positional OUTPUT when using --batch; use --out instead")
         out_dir = args.out or args.input
@@ -131,7 +140,8 @@ def main(argv=None):
             logger.info("No files to compress — all already exist.")
             return None
         results = _run_pool(_compress_job, [(f, os.path.join(out_dir, os.path.basename(f) + ".fwav"), args.tile,
-                                             args.energy_thresh, args.gpu, args.embedding, args.emb_dim, args.compact)
+                                             args.energy_thresh, args.gpu, args.embedding, args.emb_dim, args.compact,
+                                             args.query)
                                             for f in todo],
                             args.workers)
         metrics_file = os.path.join(out_dir, "compression_metrics.json")
@@ -143,7 +153,7 @@ def main(argv=None):
     if args.cmd == "decompress":
         if not args.batch:
             out_file = args.out or (os.path.splitext(args.input)[0] + "_recon.wav")
-            return _decompress_job((args.input, out_file, args.iter, args.eps, args.gpu))
+            return _decompress_job((args.input, out_file, args.iter, args.eps, args.gpu, args.s_damping))
         out_dir = args.out or args.input
         files = [os.path.join(args.input, f) for f in os.listdir(args.input) if f.lower().endswith(".fwav")]
         todo = [f for f in files
@@ -153,7 +163,8 @@ def main(argv=None):
             logger.info("No files to decompress — all already exist.")
             return None
         results = _run_pool(_decompress_job, [(f, os.path.join(out_dir, os.path.basename(f).replace(".fwav", "_recon.wav")),
-                                               args.iter, args.eps, args.gpu) for f in todo], args.workers)
+                                               args.iter, args.eps, args.gpu, args.s_damping) for f in todo],
+                            args.workers)
         metrics_file = os.path.join(out_dir, "decompression_metrics.json")
         os.makedirs(os.path.dirname(metrics_file) or ".", exist_ok=True)
         with open(metrics_file, "w") as mf:

@@ -14,6 +14,8 @@ Reference map (``/root/reference/fractal.py``):
   _process_gpu_batch :757-850                              → fwav_affine
   decompress_audio :1378-1473                              → fwav_decode
   (no counterpart; opt-in) the pool rows that :1414 reads   → fwav_compact_domains (compact_device / compact_arrays)
+  (no counterpart call; opt-in) range_candidates_from_embedding :337-351, each range's own embedding as its query
+                                                           → fwav_embed_rows + fwav_prune_q / fwav_sim_topk_q / …
 """
 from __future__ import annotations
 
@@ -75,6 +77,26 @@ def check_embedding(embedding: str, rs: int) -> str:
     return embedding
 
 
+#: query → where range i's query vector comes from: domain-embedding row i (the reference's pipeline, quirk Q1) or
+#: the embedding of the range itself (what fractal.py:337-351 computes and the pipeline never calls)
+QUERIES = ("domain_row", "range")
+#: the largest K of the search with a query table of its own (fwav_sim_topk_q)
+QUERY_RANGE_MAX_K = 64
+
+
+def check_query(query: str, emb_dim: int = 16, top_k: int | None = None) -> str:
+    """``query`` validated (no device work): ValueError for a name other than "domain_row" and "range", and for "range"
+    together with emb_dim=32 or top_k > 64 (neither is built)."""
+    if query not in QUERIES:
+        raise ValueError(f"query must be 'domain_row' or 'range', not {query!r}")
+    if query == "range":
+        if emb_dim != 16:
+            raise ValueError("query='range' with emb_dim=32 is out of scope: use emb_dim=16")
+        if top_k is not None and int(top_k) > QUERY_RANGE_MAX_K:
+            raise ValueError(f"query='range' supports top_k <= {QUERY_RANGE_MAX_K}, not {int(top_k)}")
+    return query
+
+
 #: the embedding widths the engine implements (compress_audio's emb_dim): 16, the reference's default, through the
 #: entry points above; 32 through the *_dim entry points of include/fwav.h
 EMB_DIMS = (16, 32)
@@ -113,9 +135,15 @@ def _topk_ws_size(dim: int, mq: int, nd: int, k: int, f16: bool) -> int:
     return size_call("fwav_sim_topk_workspace_size", mq, nd, k) if (f16 or k > 64) else 0
 
 
-def _sim_topk(dim, emb, emb16, nd, active_ptr, n_active_ptr, mq, lo, k, threads, cand, ties, wsk, wk, st) -> None:
-    """fwav_sim_topk, or fwav_sim_topk_dim on rows of ``dim`` != 16 columns (emb16 then its fp16 table)."""
-    if dim == 16:
+def _sim_topk(dim, emb, emb16, nd, active_ptr, n_active_ptr, mq, lo, k, threads, cand, ties, wsk, wk, st,
+              xq=None) -> None:
+    """fwav_sim_topk, or fwav_sim_topk_dim on rows of ``dim`` != 16 columns (emb16 then its fp16 table), or with
+    ``xq`` = (qemb, qemb16, n_query_rows, seed_stride) fwav_sim_topk_q."""
+    if xq is not None:
+        qemb, qemb16, nq, stride = xq
+        call("fwav_sim_topk_q", emb.data_ptr(), _p(emb16), nd, qemb.data_ptr(), _p(qemb16), nq, stride, active_ptr,
+             n_active_ptr, mq, lo, k, threads, cand.data_ptr(), _p(ties), wsk.data_ptr(), wk, st)
+    elif dim == 16:
         call("fwav_sim_topk", emb.data_ptr(), _p(emb16), nd, active_ptr, n_active_ptr, mq, lo, k, threads,
              cand.data_ptr(), _p(ties), wsk.data_ptr(), wk, st)
     else:
@@ -123,9 +151,13 @@ def _sim_topk(dim, emb, emb16, nd, active_ptr, n_active_ptr, mq, lo, k, threads,
              cand.data_ptr(), _p(ties), wsk.data_ptr(), wk, st)
 
 
-def _tie_check(dim, rsh, m, rs, cand, k, pool, nd, emb, lo, threads, ties, max_ties, mode, resolve, st) -> None:
-    """fwav_tie_check, or fwav_tie_check_dim on rows of ``dim`` != 16 columns."""
-    if dim == 16:
+def _tie_check(dim, rsh, m, rs, cand, k, pool, nd, emb, lo, threads, ties, max_ties, mode, resolve, st,
+               qemb=None) -> None:
+    """fwav_tie_check, or fwav_tie_check_dim on rows of ``dim`` != 16 columns, or with a query table fwav_tie_check_q."""
+    if qemb is not None:
+        call("fwav_tie_check_q", rsh.data_ptr(), m, rs, cand.data_ptr(), k, pool.data_ptr(), nd, emb.data_ptr(),
+             qemb.data_ptr(), lo, threads, ties.data_ptr(), max_ties, mode, resolve.data_ptr(), st)
+    elif dim == 16:
         call("fwav_tie_check", rsh.data_ptr(), m, rs, cand.data_ptr(), k, pool.data_ptr(), nd, emb.data_ptr(), lo,
              threads, ties.data_ptr(), max_ties, mode, resolve.data_ptr(), st)
     else:
@@ -159,6 +191,7 @@ class DeviceCompressed:
     ranges: Optional[torch.Tensor] = None
     pool: Optional[torch.Tensor] = None
     emb: Optional[torch.Tensor] = None
+    qemb: Optional[torch.Tensor] = None  # query="range": the ranges' own embeddings f32[n_ranges·16] (keep_intermediates)
     cand: Optional[torch.Tensor] = None
     idx: Optional[torch.Tensor] = None
     s: Optional[torch.Tensor] = None
@@ -257,7 +290,7 @@ def _compress_device(sig: torch.Tensor, tile_size: int, top_k: int, energy_thres
                      search: str = "f16", on_pool=None, blas_threads: Optional[int] = None,
                      tie_order: str = "numpy", defer_ties: bool = False,
                      sub_blocks: Optional[int] = None, embedding: str = "matrix",
-                     emb_dim: int = 16) -> DeviceCompressed:
+                     emb_dim: int = 16, query: str = "domain_row") -> DeviceCompressed:
     """Run the compress hot path on ``sig`` (1-D float32 tensor on a HIP device).
 
     ``shard=(lo, hi)`` restricts candidate search and the affine solve to ranges ``[lo, hi)`` (the
@@ -287,6 +320,13 @@ def _compress_device(sig: torch.Tensor, tile_size: int, top_k: int, energy_thres
     them through the ``*_dim`` entry points (K ≤ 64: fp16 pre-filter + exact rescoring, fwav_topk_wide.hip); every
     option above works on top, except ``embedding="pocketfft"`` (ValueError) and ``search="f32"`` (ValueError: the
     wide search has one kernel); any other width is NotImplementedError.
+    ``query="range"`` (opt-in; the default "domain_row" is the reference's pipeline, quirk Q1) searches with each
+    range's own embedding — multi_head_embedding(ranges[i]), what the reference's range_candidates_from_embedding
+    computes (fractal.py:337-351), through the same embedding kernel as the pool rows (``embedding`` honoured) — and
+    everything after the query vector follows the same contract: the prune, the zero_cand row of an all-zero query,
+    scores in the sgemv order of ``blas_threads``, numpy's tie order, the affine solve.  There is no Q9 error then
+    (n_ranges > n_domains is legal: the queries do not index the domain table).  ValueError with emb_dim=32 or
+    top_k > 64.
     """
     if sig.dim() != 1 or sig.dtype != torch.float32 or not sig.is_cuda:
         raise ValueError("compress_device expects a 1-D float32 device tensor")
@@ -308,6 +348,7 @@ def _compress_device(sig: torch.Tensor, tile_size: int, top_k: int, energy_thres
         raise ValueError(f"top_k={k} > {size_call('fwav_topk_max_k')} is not supported by the HIP search")
     check_embedding(embedding, rs)
     dim = check_emb_dim(emb_dim, embedding)
+    check_query(query, dim, k)
     if tie_order not in TIE_MODES:
         raise ValueError("tie_order must be 'numpy' (the reference's order of exactly tied scores wherever it decides a"
                          " match), 'numpy_sets' (and wherever it decides a candidate set), 'numpy_rows' (and wherever it"
@@ -322,7 +363,7 @@ def _compress_device(sig: torch.Tensor, tile_size: int, top_k: int, energy_thres
     _mark(events, "voiced_ranges")
     res = DeviceCompressed(nr, rs, tile_size, step, energy_thresh, n, nd, k, (0, nr), energy_partial=partial,
                            stream=torch.cuda.current_stream(dev))
-    if n < tile_size or nr > nd:
+    if n < tile_size or (nr > nd and query != "range"):
         # the reference returns the empty tuple for silent input before it ever builds domains
         if res.is_silent() or n < tile_size:
             return _empty(n, rs, tile_size, step, energy_thresh, k)
@@ -351,6 +392,18 @@ def _compress_device(sig: torch.Tensor, tile_size: int, top_k: int, energy_thres
     _mark(events, "pool_embed")
     if on_pool is not None:
         on_pool(pool)
+    qemb = xq = None
+    if query == "range":
+        # every range's own embedding, by the pool rows' kernel (the whole signal's: a shard's queries are rows lo … hi)
+        _mark(events, "embed_rows")
+        qemb = torch.empty(nr * 16, dtype=torch.float32, device=dev)
+        qemb16 = (torch.empty(size_call("fwav_emb16_elems", nr), dtype=torch.float16, device=dev)
+                  if emb16 is not None else None)
+        call("fwav_embed_rows_exact" if embedding == "pocketfft" else "fwav_embed_rows", ranges.data_ptr(), nr, rs,
+             tab.data_ptr(), qemb.data_ptr(), _p(qemb16), st)
+        _mark(events, "embed_rows")
+        # the first pass seeds range i's limit around the domain whose window starts where the range does
+        xq = (qemb, qemb16, nr, rs // step)
     # multi-GPU: bounds chosen from the ranges themselves (fwav.dist balances the prune); evaluated after the pool and
     # embedding kernels are queued, so its host synchronisation overlaps them
     if callable(shard):
@@ -372,7 +425,10 @@ def _compress_device(sig: torch.Tensor, tile_size: int, top_k: int, energy_thres
     if m > 0:
         _mark(events, "prune")
         zc = _zero_cand_device(nd, k, dev)
-        if dim != 16:
+        if qemb is not None:
+            call("fwav_prune_q", rsh.data_ptr(), m, lo, rs, float(F32(energy_thresh * 0.75)), int(bool(fast_mode)),
+                 qemb.data_ptr(), nr, nd, k, zc.data_ptr(), cand.data_ptr(), active.data_ptr(), n_active.data_ptr(), st)
+        elif dim != 16:
             call("fwav_prune_dim", rsh.data_ptr(), m, lo, rs, float(F32(energy_thresh * 0.75)), int(bool(fast_mode)),
                  emb.data_ptr(), nd, dim, k, zc.data_ptr(), cand.data_ptr(), active.data_ptr(), n_active.data_ptr(), st)
         else:
@@ -399,7 +455,7 @@ def _compress_device(sig: torch.Tensor, tile_size: int, top_k: int, energy_thres
             ties = (torch.empty(size_call("fwav_tie_list_size", m), dtype=torch.int32, device=dev)
                     if tie_order != "index" else None)
             _sim_topk(dim, emb, emb16, nd, active.data_ptr(), n_active.data_ptr(), m, lo, k, threads, cand, ties, wsk,
-                      wk, st)
+                      wk, st, xq)
             _mark(events, "sim_topk")
             _mark(events, "affine")
             call("fwav_affine", rsh.data_ptr(), m, rs, cand.data_ptr(), k, pool.data_ptr(), nd, sc, idx.data_ptr(),
@@ -409,7 +465,8 @@ def _compress_device(sig: torch.Tensor, tile_size: int, top_k: int, energy_thres
             # exactly tied scores whose order can change a match: numpy's own ranking for those rows (fwav.ties)
             _mark(events, "ties")
             resolve = torch.empty(m + 1, dtype=torch.int32, device=dev)
-            _tie_check(dim, rsh, m, rs, cand, k, pool, nd, emb, lo, threads, ties, m, TIE_MODES[tie_order], resolve, st)
+            _tie_check(dim, rsh, m, rs, cand, k, pool, nd, emb, lo, threads, ties, m, TIE_MODES[tie_order], resolve, st,
+                       qemb)
 
             def finish(stream_id):
                 counts = torch.stack([ties[0], resolve[0]]).cpu()
@@ -417,7 +474,7 @@ def _compress_device(sig: torch.Tensor, tile_size: int, top_k: int, energy_thres
                 if res.n_resolved:
                     _ties.resolve_rows(resolve[1:1 + res.n_resolved], emb=emb, n_domains=nd, q_offset=lo, k=k,
                                        threads=threads, emb_dim=dim, ranges=rsh, range_size=rs, pool=pool, s_clip=sc, cand=cand,
-                                       outs=(idx, s, o, sym, err), stream=stream_id)
+                                       outs=(idx, s, o, sym, err), stream=stream_id, qemb=qemb)
 
             def stage(stream_id):
                 # deferred: on the driver thread, the counts, the exact score rows and their copies; numpy's ranking
@@ -428,7 +485,8 @@ def _compress_device(sig: torch.Tensor, tile_size: int, top_k: int, energy_thres
                     return None
                 rows = resolve[1:1 + res.n_resolved]
                 futs = _ties.rank_rows(_ties.score_row_launches(rows, emb=emb, n_domains=nd, q_offset=lo,
-                                                                threads=threads, stream=stream_id, emb_dim=dim),
+                                                                threads=threads, stream=stream_id, emb_dim=dim,
+                                                                qemb=qemb),
                                        res.n_resolved, nd, k)
                 return rows, futs
 
@@ -447,10 +505,10 @@ def _compress_device(sig: torch.Tensor, tile_size: int, top_k: int, energy_thres
         elif sliced:
             ties = _search_sub_blocks(nsub, m, nd, k, lo, rs, threads, sc, tie_order, emb, emb16, active, n_active,
                                       rsh, pool, cand, (idx, s, o, sym, err), res, events, st, defer=defer_ties,
-                                      dim=dim)
+                                      dim=dim, xq=xq)
     res.pool, res.idx, res.s, res.o, res.sym, res.err, res.n_active = pool, idx, s, o, sym, err, n_active
     if keep_intermediates:
-        res.ranges, res.emb, res.cand, res.active = ranges, emb, cand, active
+        res.ranges, res.emb, res.cand, res.active, res.qemb = ranges, emb, cand, active, qemb
         if m > 0 and ties is not None:
             res.ties = ties
         if m > 0 and not sliced:
@@ -493,13 +551,14 @@ class _Staged:
 
 
 def _search_sub_blocks(nsub, m, nd, k, lo, rs, threads, sc, tie_order, emb, emb16, active, n_active, rsh, pool, cand,
-                       outs, res, events, st, defer=False, dim=16):
+                       outs, res, events, st, defer=False, dim=16, xq=None):
     """The search as ``nsub`` launches over consecutive slices of the active list.  After each slice's search and tie
     check the host reads its tie counts (one synchronisation), queues the exact score rows of its tied rows and hands
     their copies and numpy's ranking to the driver thread (fwav.ties.rank_rows_async); then the next slice searches.
     The affine solve runs once over the shard after the last slice, then the ranked rows are applied.  Returns the
-    slices' tie records as one list."""
+    slices' tie records as one list.  ``xq``: the query table of a query="range" search (_sim_topk)."""
     dev = rsh.device
+    qemb = None if xq is None else xq[0]
     bounds = _slice_bounds(m, nsub)
     wk = max(_topk_ws_size(dim, b - a, nd, k, emb16 is not None) for a, b in bounds)
     wsk = torch.empty(max(wk, 16), dtype=torch.uint8, device=dev)
@@ -511,9 +570,11 @@ def _search_sub_blocks(nsub, m, nd, k, lo, rs, threads, sc, tie_order, emb, emb1
         mq = j1 - j0
         na = torch.clamp(n_active - j0, 0, mq).to(torch.int32)
         ties = torch.empty(size_call("fwav_tie_list_size", mq), dtype=torch.int32, device=dev)
-        _sim_topk(dim, emb, emb16, nd, active[j0:].data_ptr(), na.data_ptr(), mq, lo, k, threads, cand, ties, wsk, wk, st)
+        _sim_topk(dim, emb, emb16, nd, active[j0:].data_ptr(), na.data_ptr(), mq, lo, k, threads, cand, ties, wsk, wk, st,
+                  xq)
         resolve = torch.empty(mq + 1, dtype=torch.int32, device=dev)
-        _tie_check(dim, rsh, m, rs, cand, k, pool, nd, emb, lo, threads, ties, mq, TIE_MODES[tie_order], resolve, st)
+        _tie_check(dim, rsh, m, rs, cand, k, pool, nd, emb, lo, threads, ties, mq, TIE_MODES[tie_order], resolve, st,
+                   qemb)
         counts = torch.stack([ties[0], resolve[0]]).cpu()
         if _ties._TRACE:
             import time
@@ -526,7 +587,7 @@ def _search_sub_blocks(nsub, m, nd, k, lo, rs, threads, sc, tie_order, emb, emb1
         if nr_j:
             rows = resolve[1:1 + nr_j]
             pend.append((rows, _ties.rank_rows_async(rows, emb=emb, n_domains=nd, q_offset=lo, k=k, threads=threads,
-                                                     stream=st, emb_dim=dim)))
+                                                     stream=st, emb_dim=dim, qemb=qemb)))
     _mark(events, "sim_topk")
     _mark(events, "affine")
     call("fwav_affine", rsh.data_ptr(), m, rs, cand.data_ptr(), k, pool.data_ptr(), nd, sc, *[t.data_ptr() for t in outs],

@@ -128,12 +128,14 @@ def _slot(i: int, numel: int) -> torch.Tensor:
 
 
 def score_row_launches(rows: torch.Tensor, *, emb: torch.Tensor, n_domains: int, q_offset: int, threads: int,
-                       stream: int, budget: int = DEVICE_ROW_BUDGET, first_row: int = 0, emb_dim: int = 16):
+                       stream: int, budget: int = DEVICE_ROW_BUDGET, first_row: int = 0, emb_dim: int = 16,
+                       qemb: torch.Tensor | None = None):
     """Yield (first row + first_row, device f32[m·nd] scores, event) per fwav_score_rows launch of at most
     ``budget`` bytes, each launch queued on the current stream (``stream``) when the generator reaches it.  A
     consumer that must hold one launch at a time delegates with ``yield from`` (a loop variable of its own would keep
     the previous launch alive while this generator allocates the next).  ``emb_dim``: the width of ``emb``'s rows (32:
-    fwav_score_rows_dim)."""
+    fwav_score_rows_dim).  ``qemb``: the table the query rows are read from when it is not ``emb`` itself
+    (fwav_score_rows_q: compress_audio(query="range"))."""
     nd = int(n_domains)
     n = rows.numel()
     per = max(1, min(n, budget // (4 * nd)))
@@ -141,7 +143,10 @@ def score_row_launches(rows: torch.Tensor, *, emb: torch.Tensor, n_domains: int,
         rb = rows[b0:b0 + per].contiguous()
         m = rb.numel()
         S = torch.empty(m * nd, dtype=torch.float32, device=rows.device)
-        if emb_dim == 16:
+        if qemb is not None:
+            call("fwav_score_rows_q", emb.data_ptr(), nd, qemb.data_ptr(), rb.data_ptr(), m, int(q_offset),
+                 int(threads), S.data_ptr(), stream)
+        elif emb_dim == 16:
             call("fwav_score_rows", emb.data_ptr(), nd, rb.data_ptr(), m, int(q_offset), int(threads), S.data_ptr(),
                  stream)
         else:
@@ -212,7 +217,7 @@ _ROWS: dict = {}
 
 
 def rank_rows_async(rows: torch.Tensor, *, emb: torch.Tensor, n_domains: int, q_offset: int, k: int, threads: int,
-                    stream: int, budget: int = PIPE_ROW_BUDGET, emb_dim: int = 16):
+                    stream: int, budget: int = PIPE_ROW_BUDGET, emb_dim: int = 16, qemb: torch.Tensor | None = None):
     """Queue the exact score rows of ``rows`` now — at most ``budget`` bytes of them, in one launch — and copy + rank
     them on the driver thread (copies on a copy stream that waits for the launches).  Returns a Future of the n row
     futures.  Used between the query sub-blocks of one search (fwav.engine), so that the next sub-block's search does
@@ -241,7 +246,7 @@ def rank_rows_async(rows: torch.Tensor, *, emb: torch.Tensor, n_domains: int, q_
         if eager:
             _EAGER_BYTES += nbytes
     first = [next(score_row_launches(rows[:per], emb=emb, n_domains=nd, q_offset=q_offset, threads=threads,
-                                     stream=stream, budget=budget, emb_dim=emb_dim))] if eager else []
+                                     stream=stream, budget=budget, emb_dim=emb_dim, qemb=qemb))] if eager else []
     rest = rows[per:] if eager else rows
 
     def job():
@@ -256,7 +261,7 @@ def rank_rows_async(rows: torch.Tensor, *, emb: torch.Tensor, n_domains: int, q_
                     side.wait_event(ready)
                     yield from score_row_launches(rest, emb=emb, n_domains=nd, q_offset=q_offset, threads=threads,
                                                   stream=side.cuda_stream, budget=budget,
-                                                  first_row=per if eager else 0, emb_dim=emb_dim)
+                                                  first_row=per if eager else 0, emb_dim=emb_dim, qemb=qemb)
         with torch.cuda.device(dev):
             return rank_rows(it(), n, n_domains, k, copy_stream=cs)
 
@@ -286,7 +291,7 @@ def apply_rows(rows: torch.Tensor, futs: list, *, ranges: torch.Tensor, range_si
 
 def resolve_rows(rows: torch.Tensor, *, emb: torch.Tensor, n_domains: int, q_offset: int, k: int, threads: int,
                  ranges: torch.Tensor, range_size: int, pool: torch.Tensor, s_clip: float, cand: torch.Tensor,
-                 outs: tuple, stream: int, emb_dim: int = 16) -> None:
+                 outs: tuple, stream: int, emb_dim: int = 16, qemb: torch.Tensor | None = None) -> None:
     """Rows (local indices, device int32) whose match depends on numpy's tie order: exact score rows in launches of up
     to DEVICE_ROW_BUDGET (fwav_score_rows reads the embedding table once per launch), copied to a ring of page-locked
     row slots (HOST_ROW_BUDGET), numpy's ranking of each row on a host thread pool as soon as it lands, the new
@@ -299,7 +304,7 @@ def resolve_rows(rows: torch.Tensor, *, emb: torch.Tensor, n_domains: int, q_off
     trace = os.environ.get("FWAV_TIES_TRACE")
     t0 = time.perf_counter()
     futs = rank_rows(score_row_launches(rows, emb=emb, n_domains=n_domains, q_offset=q_offset, threads=threads,
-                                        stream=stream, emb_dim=emb_dim), n, n_domains, k)
+                                        stream=stream, emb_dim=emb_dim, qemb=qemb), n, n_domains, k)
     t1 = time.perf_counter()
     for f in futs:
         f.result()

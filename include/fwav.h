@@ -184,6 +184,45 @@ int fwav_tie_rows_out(const int32_t* rows, int64_t n, const int32_t* idx_in, con
  * sink: one float of device memory. */
 int fwav_debug_gather_rows(const float* table, int64_t n_rows, int rs, int64_t n, float* sink, void* stream);
 
+/* ------------------------------------------------------------------- queries from a table of their own
+ * compress_audio(query="range"): the query of range i is multi_head_embedding(ranges[i]) — what the reference's
+ * range_candidates_from_embedding computes (fractal.py:337-351) and its pipeline never calls — instead of domain
+ * row i (quirk Q1).  Opt-in: no other entry point calls these, and fwav_abi_version is unchanged (additions only).
+ *   fwav_embed_rows / fwav_embed_rows_exact: the embedding half of fwav_pool_embed / fwav_pool_embed_exact on n caller
+ *     rows of range_size floats (rows f32[n·range_size], 4-B aligned) — the same kernels reading other rows, so each
+ *     has the accuracy contract of the entry point it mirrors: bit-exact at range sizes 4, 8 and 16, bit-exact in the
+ *     exact variant at every range size with a plan (FWAV_ERR_ARG at any other), the f64-matrix bars elsewhere.  tab as
+ *     for the mirrored call.  emb f32[n·16]; emb16 (optional) f16[fwav_emb16_elems(n)], the tiled hi/lo layout of
+ *     fwav_emb16_from_emb.  Every head of a row has norm ≤ 1, as a pool row's has (the search's error bounds need it).
+ *   fwav_prune_q, fwav_sim_topk_q, fwav_score_rows_q, fwav_tie_check_q: the entry points they are named after, with
+ *     local query i read from row q_offset + i of the QUERY table — qemb f32[n_query_rows·16] and its tiled fp16 parts
+ *     qemb16 f16[fwav_emb16_elems(n_query_rows)] (NULL exactly where emb16 is) — while the candidates are rows of emb.
+ *     n_query_rows may exceed n_domains.  Everything else is the named entry point's contract: the energy prune, the
+ *     zero_cand row of an all-zero query, scores in the sgemv order of blas_threads, (score desc, index asc) order, the
+ *     tie list and its check; workspace sizes are fwav_sim_topk_workspace_size's.  fwav_sim_topk_q serves K ≤ 64
+ *     (FWAV_ERR_K above) and needs every head of a query row to have norm ≤ 1.
+ *     seed_stride ≥ 0: the first pass seeds query row r's band limit from the window of table rows centred at
+ *     min(r·seed_stride, n_domains − 1); any window of K in-table rows gives a valid lower bound, so it only moves the
+ *     starting limit (compress_audio passes range_size / domain_step, the row whose window starts where the range
+ *     does).  With qemb = emb, qemb16 = emb16 and seed_stride = 1 the result is fwav_sim_topk's. */
+int fwav_embed_rows(const float* rows, int64_t n, int range_size, const double* tab, float* emb, void* emb16,
+                    void* stream);
+int fwav_embed_rows_exact(const float* rows, int64_t n, int range_size, const double* tab, float* emb, void* emb16,
+                          void* stream);
+int fwav_prune_q(const float* ranges, int64_t n, int64_t q_offset, int range_size, float prune_thr, int fast_mode,
+                 const float* qemb, int64_t n_query_rows, int64_t n_domains, int k, const int32_t* zero_cand,
+                 int32_t* cand, int32_t* active, int32_t* n_active, void* stream);
+int fwav_sim_topk_q(const float* emb, const void* emb16, int64_t n_domains, const float* qemb, const void* qemb16,
+                    int64_t n_query_rows, int seed_stride, const int32_t* active, const int32_t* n_active,
+                    int64_t max_q, int64_t q_offset, int k, int blas_threads, int32_t* cand, int32_t* ties,
+                    void* workspace, size_t ws_bytes, void* stream);
+int fwav_score_rows_q(const float* emb, int64_t n_domains, const float* qemb, const int32_t* rows, int64_t n_rows,
+                      int64_t q_offset, int blas_threads, float* scores, void* stream);
+int fwav_tie_check_q(const float* ranges, int64_t n_ranges, int range_size, const int32_t* cand, int k,
+                     const float* pool, int64_t n_domains, const float* emb, const float* qemb, int64_t q_offset,
+                     int blas_threads, const int32_t* ties, int64_t max_ties, int exact_sets, int32_t* resolve,
+                     void* stream);
+
 /* ------------------------------------------------------------------- compact domain pool
  * Keeps only the domain rows that some match names and renumbers the matches.  decompress_audio reads
  * domains[idx[i]] and nothing else (fractal.py:1414), and a .fwav stores its own n_domains (save_compressed /

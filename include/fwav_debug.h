@@ -18,6 +18,15 @@ extern "C" {
 int fwav_debug_sim_topk(const float* emb, const void* emb16, int64_t n_domains, const int32_t* active,
                         const int32_t* n_active, int64_t max_q, int64_t q_offset, int k, int32_t* cand,
                         void* workspace, size_t ws_bytes, int dbg, unsigned long long* stats, void* stream);
+/* fwav_debug_sim_topk with the queries of fwav_sim_topk_q (fwav.h, "queries from a table of their own"): the forced
+ * geometry, cent-sets, mode, floor and plan knobs below apply to it alike. */
+int fwav_debug_sim_topk_q(const float* emb, const void* emb16, int64_t n_domains, const float* qemb,
+                          const void* qemb16, int64_t n_query_rows, int seed_stride, const int32_t* active,
+                          const int32_t* n_active, int64_t max_q, int64_t q_offset, int k, int32_t* cand,
+                          void* workspace, size_t ws_bytes, int dbg, unsigned long long* stats, void* stream);
+/* Host, no device: the table row at which fwav_sim_topk_q's first pass centres the seed window of query row `row`,
+ * min(row * seed_stride, n_domains - 1), through the kernels' own code; -1 for a negative argument or no domains. */
+int64_t fwav_debug_seed_centre(int64_t row, int seed_stride, int64_t n_domains);
 /* The three overrides below (fwav_debug_topk_plan / _mode / _geometry) are PROCESS-GLOBAL test knobs, not thread-safe:
  * they change which kernels fwav_sim_topk launches and how much workspace it needs, so set them only while no search
  * is being sized or is in flight on any thread, and re-query fwav_sim_topk_workspace_size after a change (a search
