@@ -323,6 +323,8 @@ def decode_beta(n: int) -> float:
 
 def decode_decision(rr: float, dd: float, delta: float, eps: float, beta: float) -> int:
     """The device's early-exit decision for the f64 Δ (fwav_decode.hip dec_decide): 1 stop, 0 go on, 2 check."""
+    if dd != dd or rr != rr:  # a NaN among the values: the reference's Δ is NaN too, and `NaN < eps` is false
+        return 0
     if dd == 0.0:
         return 1 if 0.0 < eps else 0
     if dd < 1e-30 or dd > 1e36 or (rr > 0.0 and (rr < 1e-30 or rr > 1e36)):

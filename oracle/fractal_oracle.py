@@ -566,7 +566,8 @@ def decode(idx, s_st, o_st, sym, pool, n_ranges, range_size, iterations=8, conve
     """decompress_audio (fractal.py:1378-1473), float32 in numpy order.  The early exit takes the reference's own
     decision: Δ = reference_delta (numpy's BLAS sdot norms, fractal.py:1460-1461) < eps.  Returns (recon f32,
     iterations_run, deltas): deltas="f64" lists Δ in float64 from exact float64 sums of the same float32 values (what the
-    device reports), deltas="reference" the reference's own float32-derived values."""
+    device reports), deltas="reference" the reference's own float32-derived values, deltas="sums" one tuple per
+    iteration (float64 Δ, reference Δ, Σ rec², Σ (next − rec)² — the two float64 sums the device decides on)."""
     idx = np.asarray(idx, np.int32).copy()
     s_st = np.asarray(s_st, F32).copy()
     o_st = np.asarray(o_st, F32).copy()
@@ -602,10 +603,12 @@ def decode(idx, s_st, o_st, sym, pool, n_ranges, range_size, iterations=8, conve
         s_used = np.clip(s_used, -c, c)
         nxt = F32(0.0) + (s_used[:, None] * tiles + o_st[:, None])   # bincount adds into +0.0
         delta = reference_delta(recon, nxt)
-        if deltas == "f64":
-            rn = float(np.sqrt(np.sum(recon.astype(np.float64) ** 2)))
-            dn = float(np.sqrt(np.sum((nxt - recon).astype(np.float64) ** 2)))  # f32 difference, as :1460
-            out_deltas.append(dn / (rn if rn > 0 else 1.0))
+        if deltas in ("f64", "sums"):
+            rr = float(np.sum(recon.astype(np.float64) ** 2))
+            dd = float(np.sum((nxt - recon).astype(np.float64) ** 2))  # f32 difference, as :1460
+            rn, dn = float(np.sqrt(rr)), float(np.sqrt(dd))
+            d64 = dn / (rn if rn > 0 else 1.0)
+            out_deltas.append(d64 if deltas == "f64" else (d64, delta, rr, dd))
         else:
             out_deltas.append(delta)
         recon = nxt

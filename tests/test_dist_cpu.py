@@ -395,3 +395,19 @@ def test_sharded_decompress_exact_check(side):
     assert info["iterations"] == it
     assert np.array_equal(rec.view(np.uint32), ref.view(np.uint32))
     assert info["deltas"][t] == dref[t]  # the checked iteration reports the reference's own Δ
+
+
+def test_decode_decision_states_dec_decide():
+    """fwav.dist.decode_decision is the host's statement of fwav_decode.hip dec_decide, arm by arm: a NaN among the
+    sums goes on without a check (the reference's Δ is NaN, and `NaN < eps` is false), zero differences stop iff
+    0 < eps, sums in float32's denormal or overflow range are always checked, and only the β band is checked else."""
+    from fwav.dist import decode_decision
+    nan, inf = float("nan"), float("inf")
+    for rr, dd in ((1.0, nan), (nan, 1.0), (nan, nan), (nan, 0.0), (inf, nan)):
+        assert decode_decision(rr, dd, nan, 1e-3, 1e-6) == 0
+    assert decode_decision(1.0, 0.0, 0.0, 1e-3, 1e-6) == 1 and decode_decision(1.0, 0.0, 0.0, 0.0, 1e-6) == 0
+    for rr, dd in ((1.0, 1e-31), (1.0, 1e37), (1e-31, 1.0), (1e37, 1.0), (inf, 1.0), (1.0, inf), (inf, inf)):
+        assert decode_decision(rr, dd, (dd / rr) ** 0.5 if rr < inf and dd < inf else nan, 1e-3, 1e-6) == 2
+    assert decode_decision(0.0, 1e-31, 1e-15, 1e-3, 1e-6) == 2 and decode_decision(0.0, 4.0, 2.0, 1e-3, 1e-6) == 0
+    assert decode_decision(1.0, 1e-8, 1e-4, 1e-3, 1e-6) == 1 and decode_decision(1.0, 1e-4, 1e-2, 1e-3, 1e-6) == 0
+    assert decode_decision(1.0, 1e-6, 1e-3 * (1 + 5e-7), 1e-3, 1e-6) == 2

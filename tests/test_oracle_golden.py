@@ -259,6 +259,72 @@ def test_sdot_blas_pinned(n):
                     assert O.sdot_blas(a, b).view(np.uint32) == np.float32(want).view(np.uint32), (n, T)
 
 
+def test_decode_edges_pinned():
+    """tests/golden/decode_edges.npz (the reference's own decompress_audio on the edge table of tests/decode_edges.py:
+    sentinel indices, constant and tiny tiles, a den pair straddling 1e-12, −0.0, s far outside s_clip, sym bytes 2 and
+    255, NaN / inf / ±3e38, the table × 1e-20, × 1e-30 and × 1e19; range sizes 1 … 1024; the twelve parameter sets):
+    the shared builder still makes the recorded inputs (SHA-256), and O.decode reproduces every recorded
+    reconstruction bit for bit (a NaN matches any NaN), the iteration count and every logged Δ — which makes O.decode
+    the reference of the wider GPU sweep (tests/test_gpu_decode_edges.py) at sizes and values the goldens never had."""
+    import json
+    import os
+
+    import decode_edges as DE
+    fx = np.load(os.path.join(os.path.dirname(__file__), "golden", "decode_edges.npz"))
+    meta = json.loads(str(fx["params"]))
+    entries = [tuple(e) for e in meta["entries"]]
+    assert entries == DE.fixture_entries() and meta["nr"] == DE.FIXTURE_NR
+    assert [tuple(p) for p in meta["params"]] == list(DE.PARAMS)
+    nr = DE.FIXTURE_NR
+    tables, seen = {}, {k: set() for k in ("nan", "stop1", "inf0")}
+    for rs, kind, pi in entries:
+        if (rs, kind) not in tables:
+            tables[rs, kind] = DE.build(rs, nr, kind)
+            assert DE.input_digest(*tables[rs, kind][:5]) == meta["inputs"][f"rs{rs}_{kind}"], (rs, kind)
+        idx, s, o, sym, pool, names = tables[rs, kind]
+        label = DE.labels(names, nr)
+        tag = f"rs{rs}_{kind}_p{pi}"
+        with np.errstate(all="ignore"):
+            rec, it, dl = O.decode(idx, s, o, sym, pool, nr, rs, deltas="reference", **DE.kw(DE.PARAMS[pi]))
+            dig = DE.row_digests(rec, nr, rs)
+        bad = [(r, label[r]) for r in range(nr) if not np.array_equal(dig[r], fx[f"dig_{tag}"][r])]
+        assert not bad, (tag, bad)
+        if f"rec_{tag}" in fx:
+            assert DE.same_bits_or_nan(rec, fx[f"rec_{tag}"]), tag
+        assert it == int(fx[f"it_{tag}"]), (tag, it, int(fx[f"it_{tag}"]))
+        want = fx[f"dl_{tag}"].tolist()
+        got = [DE.fmt_delta(v) for v in dl]
+        assert len(got) == len(want) and all(a == b or (a != a and b != b) for a, b in zip(got, want)), (tag, got, want)
+        # the regimes the table is there for, read off the reference's own record
+        if any(v != v for v in want):
+            seen["nan"].add(kind)
+        if it == 1 and DE.PARAMS[pi][0] > 1:
+            seen["stop1"].add(kind)
+        if len(want) >= 2 and want[0] == float("inf") and want[1] == 0.0 and it == 2:
+            seen["inf0"].add(kind)
+    assert "nonfinite" in seen["nan"] and {"tiny", "flush"} <= seen["stop1"] and "huge" in seen["inf0"], seen
+
+
+@pytest.mark.parametrize("n", [33, 64, 1000, 65537])
+@pytest.mark.parametrize("scale", [1e-20, 1e19])
+def test_sdot_blas_pinned_denormal_and_overflow(n, scale):
+    """test_sdot_blas_pinned with products in float32's denormal range (× 1e-20) and beyond its largest value
+    (× 1e19): O.sdot_blas equals numpy's own x.dot(x) bit for bit there too — the norms of the decode's Δ at tiny and
+    at overflowing reconstructions."""
+    from threadpoolctl import threadpool_limits
+    rng = np.random.default_rng(n)
+    x = (rng.standard_normal(n) * np.exp(rng.uniform(-4, 4, n))).astype(np.float32) * np.float32(scale)
+    y = (rng.standard_normal(n).astype(np.float32) * np.float32(0.3)) * np.float32(scale)
+    for T in (1, 8):
+        with threadpool_limits(T, user_api="blas"), np.errstate(all="ignore"):
+            for a in (x, y):
+                want = np.float32(a.dot(a))
+                got = O.sdot_blas(a, a)
+                assert got.view(np.uint32) == want.view(np.uint32), (n, T, got, want)
+    with np.errstate(all="ignore"):   # the products really are denormal / really overflow
+        assert np.isinf(np.float32(x.dot(x))) if scale > 1 else bool(np.all(y * y < np.float32(1.2e-38)))
+
+
 def test_cfg2_tuple_fixture_pinned():
     """tests/golden/cfg2_tuples_t16.npz (every cfg2 match tuple with 16 BLAS threads, make_cfg2_tuples.py) against
     the oracle recomputed here on 256 sampled untied rows plus 8 of its numpy-ranked tie rows: same embedding table
