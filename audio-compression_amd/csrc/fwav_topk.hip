@@ -145,6 +145,16 @@ struct QueryTab {
   int seed_stride = 1;
 };
 
+// The first pass's seed policy (seed_limit): 0 = where a floor is applied, one probe at the floor decides per query set
+// whether the seeds' bit search runs; 1 = always the search; 2 = never seed.  Every policy returns the same candidates.
+#ifdef FWAV_DEBUG_API
+static int g_seed_mode = 0;  // fwav_debug_topk_seeds (debug library only)
+constexpr bool kSeedKnob = true;
+#else
+constexpr int g_seed_mode = 0;
+constexpr bool kSeedKnob = false;  // the product's kernels do not read FloorCtl::seeds
+#endif
+
 #include "fwav_topk_f32.h"
 #include "fwav_topk_plan.h"
 #include "fwav_topk_floor.h"
@@ -602,6 +612,7 @@ static int launch_topk(const float* emb, const _Float16* emb16, int64_t nd, cons
     // (with a floor the device runs the floor-free plan fl.alt_* when the floor did not apply: the grid, the shared
     // limits and the merge cover both plans)
     auto first_pass = [&](const int32_t* act, const int32_t* nact, int g, int rt, int P, FloorCtl fl, bool diag) {
+      fl.seeds = g_seed_mode;
       const TopkPlan pl0 = make_plan(max_q, rt, P, geometry_qb(g));
       const TopkPlan pla = fl.key != nullptr ? make_plan(max_q, fl.alt_rt, fl.alt_p, geometry_qb(g)) : pl0;
       struct {
@@ -926,6 +937,14 @@ int fwav_debug_topk_floor(int mode, float value) {
   uint32_t u;
   std::memcpy(&u, &value, sizeof u);
   g_floor_key = (u & 0x80000000u) ? ~u : (u | 0x80000000u);  // f2key
+  return FWAV_OK;
+}
+
+// Diagnostic override of the first passes' seed policy (include/fwav_debug.h): 0 = probe at the floor, then search
+// (the default), 1 = always search, 2 = never seed.
+int fwav_debug_topk_seeds(int mode) {
+  FWAV_CHECK_ARG(mode >= 0 && mode <= 2, FWAV_ERR_ARG, "fwav_debug_topk_seeds: mode outside [0, 2]");
+  g_seed_mode = mode;
   return FWAV_OK;
 }
 

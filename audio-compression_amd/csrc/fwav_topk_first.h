@@ -59,7 +59,12 @@ constexpr int kGrow = 64;           // ... and growth since the last compaction
 // so the instrumentation adds no global atomics to the measured loop.
 // [12] ticks waiting for the group's own chunk DMA (vmcnt at the group top; [7] is then the barrier alone),
 //   [13] centroid level-1 ticks, [14] centroid level-2 (tile, set) pairs
+// The prologue's counters live in slots of their own, [16 .. kStatsX), which only the STATS kernels' LDS rows have and
+// which reach the caller's array only on request (dbg 64: callers that pass u64[16] are never written past it):
+//   [16] ticks in the prologue (kernel start to the first group's DMA)  [17] ticks in its seed phase
+//   [18] (query set, item) pairs that ran the seeds' full bit search
 constexpr int kStats = 16;
+constexpr int kStatsX = 20;
 __device__ __forceinline__ void stat_add_p(unsigned long long* stats, int i, unsigned long long v) {
   if (stats != nullptr && (threadIdx.x & 63) == 0) stats[i] += v;
 }
@@ -111,7 +116,7 @@ struct Topk16SmemT {
   int64_t qrow[32 * NG];
   int32_t qpos[32 * NG];  // position of the slot's query in the active list (index of its shared band limit)
   uint32_t fired[FIFO ? NG : 1][kFifo];            // deferred work: ring of fired chunk entries (not in CENT)
-  unsigned long long wstat[STATS ? NW : 1][kStats];  // STATS builds only (one row per wave)
+  unsigned long long wstat[STATS ? NW : 1][STATS ? kStatsX : kStats];  // STATS builds only (one row per wave)
 };
 // The per-query rows of the centroid geometry with 4 query sets per wave (1,024 queries per workgroup: S16 / HL
 // passes only): 14 B per query instead of 28, so that two workgroups' 2 × G chunk slots still fit a CU's LDS.  The
@@ -134,7 +139,7 @@ struct Topk16SmemColdT {
   int ovf[32 * NG];
   int32_t qpos[32 * NG];
   ZeroRow tie;
-  unsigned long long wstat[STATS ? NW : 1][kStats];
+  unsigned long long wstat[STATS ? NW : 1][STATS ? kStatsX : kStats];
 };
 
 // Streaming compaction on shl keys (no f32 rescoring, no table loads, no sort): S = the K-th largest shl in the
@@ -670,9 +675,21 @@ __host__ __device__ __forceinline__ int64_t seed_centre(int64_t qrow, const Quer
 constexpr int kSeedTiles = (2 * kSeedHalf + 62) / 32 + 1;  // the wave's 32 windows from a tile-aligned base
 // LEAN (the 4-set centroid geometry, whose prologue holds 4 sets' fragments): the tiles' addresses as wave-uniform
 // offsets (wbase is uniform) plus one per-lane index, instead of a 64-bit pointer per tile and lane.
+// Probe (launches with an applied floor f, `probe`: wave-uniform): one count at f decides for the whole set whether the
+// bit search runs.  The count is monotone in its threshold, so a query with fewer than K window scores ≥ f ends the
+// search at a key below f's, its seed key2f(T) − 2δ lies below f, and the caller's max(seed, f) is f; when no live
+// lane of the set (`live`: the slot takes appends) counts K, the search is skipped and −∞ returned for all of them,
+// else it runs in full and returns what it always did.  The caller's limit is the same bit for bit on every input;
+// on white noise almost no set passes the probe.  `searched` is set where the bit search ran.
+// Measured (profiles/r09/): cfg2 runs the search for 921 of 31,008 (set, item) pairs, the prologue falls from 4.9 to
+// 0.95 % of wave time (no seeds at all: 0.26 %); first pass 10.22 → 9.84 ms (kernel trace, 25 launches), search against
+// the previous library, same process, identical candidates, both orders: 330,750 queries 11.34 / 11.39 → 11.00 /
+// 11.05 ms, 165,375 6.99 / 7.03 → 6.57 / 6.58, 82,688 4.16 / 4.05 → 4.02 / 3.90, 41,344 2.44 / 2.45 → 2.32 / 2.34;
+// never seeding (fwav_debug_topk_seeds(2)) is the ceiling: 330,750 queries 11.55 → 10.87 where the probe gives 11.07.
 template <int MODE, bool LEAN = false>
 __device__ __forceinline__ float seed_limit(const _Float16* __restrict__ emb16, int64_t nd, half8 b, int64_t qrow,
-                                            int64_t wbase, int K) {
+                                            int64_t wbase, int K, bool probe, float floor, bool live,
+                                            bool& searched) {
   const int lane = threadIdx.x & 63;
   const int col = lane & 31;
   const int h = lane >> 5;
@@ -709,14 +726,24 @@ __device__ __forceinline__ float seed_limit(const _Float16* __restrict__ emb16, 
     return c + __shfl_xor(c, 32);
   };
   // No per-lane branches here: the MFMAs and shuffles need the whole wave active (a per-lane early return let the
-  // compiler run the select loop under a partial EXEC, which corrupts both)
-  const bool ok = count_ge(0.0f) >= K;
-  uint32_t T = 0x80000000u;  // key of +0.0
-  for (int bit = 30; bit >= 12; --bit) {
-    const uint32_t Tc = T | (1u << bit);
-    const int c = count_ge(key2f(Tc));
-    T = c >= K ? Tc : T;
+  // compiler run the select loop under a partial EXEC, which corrupts both); the probe's branch is wave-uniform
+  // One loop, one call of count_ge (the probe as a call of its own before the search, with a wave-uniform return,
+  // compiled the 4-set kernel to 476 B of scratch per lane; this form to 8 B, the search without a probe to 28 B):
+  // step 32 is the probe, step 31 tests key 0x80000000 (+0.0: the window holds K scores ≥ 0, else −∞ is
+  // returned whatever the later steps find), steps 30 … 12 the bits below it.
+  uint32_t T = 0u;
+  bool run = true;  // wave-uniform
+  for (int bit = probe ? 32 : 31; bit >= 12 && run; --bit) {
+    const bool pr = bit == 32;
+    const uint32_t Tc = T | (1u << (bit & 31));
+    const int c = count_ge(pr ? floor : key2f(Tc));
+    if (pr)
+      run = __ballot(live && c >= K) != 0ull;
+    else
+      T = c >= K ? Tc : T;
   }
+  searched = run;
+  const bool ok = (T & 0x80000000u) != 0u;
   return ok ? (MODE == kModeHL ? key2f(T) - kF16Delta - 2.0f * kHLDelta : key2f(T) - 2.0f * kF16Delta) : -INFINITY;
 }
 
@@ -1024,7 +1051,7 @@ __global__ __launch_bounds__(64 * W, MODE == kModeEX ? kExactWavesPerSimd : (CEN
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // provably uniform: scalar control flow below
   unsigned long long* stats = nullptr;
   if (STATS) {
-    if (lane < kStats) sm.wstat[wave][lane] = 0;
+    if (lane < kStatsX) sm.wstat[wave][lane] = 0;
     stats = sm.wstat[wave];
   }
   const int col = lane & 31;
@@ -1033,7 +1060,8 @@ __global__ __launch_bounds__(64 * W, MODE == kModeEX ? kExactWavesPerSimd : (CEN
   // 2 = skip MFMA + threshold test, 4 = no global chunk loads, 128 = DMA only every other chunk,
   // 256 = no group barrier, 512 = fold without ballots, 1024 = MFMA without fold, 4096 = record the workgroup
   // timeline (combinable with the others), 8192 = no seeded band limits; 2048 = the centroid filter with its
-  // worst-case slack alone (outputs valid: the A/B of the score-dependent bound)
+  // worst-case slack alone (outputs valid: the A/B of the score-dependent bound); 64 = the prologue's
+  // counters at gstats[16 .. 19], the seed dump and the timeline from gstats[32] on (outputs valid)
   if (!STATS) dbg = FWAV_TOPK_ABL;  // production: 0; ablation builds (-DFWAV_TOPK_ABL=bits) fix the bits at compile time
   half8 b[QS], bl[QS];  // the query's fp16 high and low parts (MFMA B operands)
   float thf[QS];        // band limit: on shl (first pass), on s16 (exact mode)
@@ -1094,7 +1122,12 @@ __global__ __launch_bounds__(64 * W, MODE == kModeEX ? kExactWavesPerSimd : (CEN
 
   // seed the band limits from the queries' own domain windows (tiles from the wave's first query row; XQ: from the
   // window of table rows around seed_centre of the query's row — any K in-table rows give a valid limit)
-  if (COLD || !(ABL && (dbg & 8192))) {  // ablation 8192: no seed
+  // (the debug library's fwav_debug_topk_seeds: 1 = the bit search for every set, floor or not; 2 = no seeds)
+  const int seed_mode = kSeedKnob ? fl.seeds : 0;
+  const bool no_seed = (ABL && (dbg & 8192)) || seed_mode == 2;  // ablation 8192: no seed
+  const bool probe = fkey != 0u && seed_mode != 1;
+  const unsigned long long t_seed = STATS ? __builtin_amdgcn_s_memrealtime() : 0;
+  if (COLD || !no_seed) {
 #pragma unroll
     for (int s = 0; s < QS; ++s) {
       // whole wave (MFMA + shuffles); lanes of unused query slots discard the result
@@ -1107,19 +1140,24 @@ __global__ __launch_bounds__(64 * W, MODE == kModeEX ? kExactWavesPerSimd : (CEN
         qrow_s = seed_centre<XQ>(qrow_q, xq, nd);
         qrow_0 = __builtin_amdgcn_readfirstlane((int)qrow_s);
         b[s] = *reinterpret_cast<const half8*>(q16 + (((qrow_q >> 8) * 2 + h) * 256 + (qrow_q & 255)) * 8);
-        if (ABL && (dbg & 8192)) continue;
+        if (no_seed) continue;
       } else {
         qrow_s = seed_centre<XQ>(sm.qrow[(wave * QS + s) * 32 + col], xq, nd);
         qrow_0 = __builtin_amdgcn_readfirstlane((int)seed_centre<XQ>(sm.qrow[(wave * QS + s) * 32], xq, nd));
       }
       const int64_t wbase = (int64_t)((qrow_0 - kSeedHalf) >> 5) << 5;
-      const float seed = seed_limit<MODE, COLD>(emb16, nd, b[s], qrow_s, wbase, K);
       // (COLD keeps no upd[]: a slot that takes no appends has thf = +∞)
-      if (COLD ? thf[s] != INFINITY : upd[s] != 0) thf[s] = seed;
+      const bool live = COLD ? thf[s] != INFINITY : upd[s] != 0;
+      bool searched;
+      const float seed = seed_limit<MODE, COLD>(emb16, nd, b[s], qrow_s, wbase, K, probe, key2f(fkey), live, searched);
+      if (live) thf[s] = seed;
+      if (STATS) stat_add(18, searched ? 1 : 0);
       if (STATS && (dbg & 32768) && gstats != nullptr && h == 0 && upd[s])  // diagnostics: the seeds
-        gstats[16 + slot_query(block, qslot0 + (wave * QS + s) * 32 + col, plan.nb)] = __float_as_uint(seed);
+        gstats[((dbg & 64) ? 2 * kStats : kStats) + slot_query(block, qslot0 + (wave * QS + s) * 32 + col, plan.nb)] =
+            __float_as_uint(seed);
     }
   }
+  if (STATS) stat_add(17, __builtin_amdgcn_s_memrealtime() - t_seed);
   if (seeds_in != nullptr) {
 #pragma unroll
     for (int s = 0; s < QS; ++s) {
@@ -1189,6 +1227,7 @@ __global__ __launch_bounds__(64 * W, MODE == kModeEX ? kExactWavesPerSimd : (CEN
   // retire the prologue's ordinary loads (query fragments, active list) before the stream, visibly to hipcc
   // (a load still pending at the loop head is waited on, vmcnt(0), inside every chunk iteration)
   __builtin_amdgcn_s_waitcnt(0x0F70);
+  if (STATS) stat_add(16, __builtin_amdgcn_s_memrealtime() - t_kernel);
   if (ngroups > 0) issue_group(0);
 
   int sink = 0;     // ablation builds: keeps the MFMA / fold results of dbg 512/1024 alive
@@ -1492,10 +1531,14 @@ __global__ __launch_bounds__(64 * W, MODE == kModeEX ? kExactWavesPerSimd : (CEN
       atomicAdd(gstats + 15, mx);
     }
     if (gstats != nullptr && lane < kStats && lane != 15) atomicAdd(gstats + lane, sm.wstat[wave][lane]);
-    // dbg 4096: workgroup timeline (start of its first wave, end of its last) at gstats[16 + 2·block]
+    // dbg 64: the prologue's counters too (the caller's array then holds 2·kStats entries before any dump)
+    if (gstats != nullptr && (dbg & 64) && lane >= kStats && lane < kStatsX)
+      atomicAdd(gstats + lane, sm.wstat[wave][lane]);
+    // dbg 4096: workgroup timeline (start of its first wave, end of its last) at gstats[16 + 2·block] (dbg 64: 32 +)
     if (gstats != nullptr && (dbg & 4096) && lane == 0) {
-      atomicMin(gstats + 16 + 2 * blockIdx.x, t_kernel);
-      atomicMax(gstats + 17 + 2 * blockIdx.x, __builtin_amdgcn_s_memrealtime());
+      const int t0 = (dbg & 64) ? 2 * kStats : kStats;
+      atomicMin(gstats + t0 + 2 * blockIdx.x, t_kernel);
+      atomicMax(gstats + t0 + 1 + 2 * blockIdx.x, __builtin_amdgcn_s_memrealtime());
     }
   }
 }

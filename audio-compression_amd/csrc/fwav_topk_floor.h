@@ -16,6 +16,9 @@ struct FloorCtl {
   int32_t* miss;
   int32_t* n_miss;
   int alt_rt = -1, alt_p = 1;
+  // the debug library's seed policy (fwav_debug_topk_seeds; read only where kSeedKnob is set: the product's kernels
+  // hold the default, 0, as a constant)
+  int seeds = 0;
 };
 // Whole wave: true (and the query listed for the second pass) when the floor may have cut a member of its top K:
 // fewer than K band entries, or a K-th exact score (kth: key) not above f + δ.  Every domain whose filter score

@@ -107,6 +107,7 @@ DEBUG_SIGNATURES = {
     "fwav_debug_topk_qb": (I64, [I32]),
     "fwav_debug_topk_floor": (I32, [I32, F32]),
     "fwav_debug_topk_floor_pieces": (I32, [I32]),
+    "fwav_debug_topk_seeds": (I32, [I32]),
     "fwav_debug_sim_topk_layout": (I32, [I64, I64, P]),
     "fwav_debug_compact_stage_ms": (I32, [P, I64, P, I64, I32, P, P, P, P, P, SZ, P, P]),
 }
@@ -165,8 +166,8 @@ def product_lib() -> C.CDLL:
 
 def debug_lib() -> C.CDLL:
     """libfwav_debug.so (include/fwav_debug.h): the same entry points plus the search's test knobs; tests only.
-    FWAV_DEBUG_TOPK_FLOOR="mode[:value]" / FWAV_DEBUG_TOPK_GEOMETRY=g set fwav_debug_topk_floor / _geometry when it
-    loads (same-box A/Bs of whole programs, e.g. bench.py under FWAV_DEBUG_LIBRARY=1)."""
+    FWAV_DEBUG_TOPK_FLOOR="mode[:value]" / FWAV_DEBUG_TOPK_GEOMETRY=g / FWAV_DEBUG_TOPK_SEEDS=m set
+    fwav_debug_topk_floor / _geometry / _seeds when it loads (same-box A/Bs of whole programs, e.g. bench.py under FWAV_DEBUG_LIBRARY=1)."""
     if "debug" not in _libs:
         _libs["debug"] = _load(DEBUG_LIB_PATH, {**SIGNATURES, **DEBUG_SIGNATURES})
         fl = os.environ.get("FWAV_DEBUG_TOPK_FLOOR")
@@ -179,6 +180,8 @@ def debug_lib() -> C.CDLL:
             _libs["debug"].fwav_debug_topk_tail(int(os.environ["FWAV_DEBUG_TOPK_TAIL"]))
         if os.environ.get("FWAV_DEBUG_TOPK_P2"):
             _libs["debug"].fwav_debug_topk_floor_pieces(int(os.environ["FWAV_DEBUG_TOPK_P2"]))
+        if os.environ.get("FWAV_DEBUG_TOPK_SEEDS"):
+            _libs["debug"].fwav_debug_topk_seeds(int(os.environ["FWAV_DEBUG_TOPK_SEEDS"]))
     return _libs["debug"]
 
 
@@ -211,6 +214,7 @@ class debug_library:
         d.fwav_debug_topk_floor(-1, 0.0)
         d.fwav_debug_topk_floor_pieces(0)
         d.fwav_debug_topk_tail(-1)
+        d.fwav_debug_topk_seeds(0)
         _active = self.prev
         return False
 

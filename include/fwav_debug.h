@@ -14,7 +14,10 @@ extern "C" {
 /* Diagnostic ablations of the fp16 kernel (timing only, outputs invalid for dbg & 65535 != 0); stats (u64[16]
  * device, may be NULL) receives slow-path counters — of the first pass, or with dbg = 1 << 17 of the exact-mode
  * relaunch for overflowed queries only (outputs valid); dbg bit 18 counts in the product's first-pass geometry
- * (else the base one), bit 19 with the product's speculative floor (else none).  Not used by the product path. */
+ * (else the base one), bit 19 with the product's speculative floor (else none).  dbg 64 (outputs valid) adds the
+ * prologue's counters: stats is then u64[32], [16] = ticks in the prologue, [17] = ticks in its seed phase, [18] =
+ * (query set, item) pairs that ran the seeds' full search; the dumps of dbg 4096 and 32768 then start at stats[32]
+ * instead of stats[16].  Not used by the product path. */
 int fwav_debug_sim_topk(const float* emb, const void* emb16, int64_t n_domains, const int32_t* active,
                         const int32_t* n_active, int64_t max_q, int64_t q_offset, int k, int32_t* cand,
                         void* workspace, size_t ws_bytes, int dbg, unsigned long long* stats, void* stream);
@@ -82,6 +85,13 @@ int64_t fwav_debug_topk_qb(int geo);
  * the default rank, with the second pass's floor `value` (≥ 0) below the pilots' smallest estimate instead of 0.15.
  * All return the same candidates. */
 int fwav_debug_topk_floor(int mode, float value);
+/* Diagnostic override of the first passes' seed policy (a query's band limit starts at the K-th best fp16 score of the
+ * 128 table rows around its own, found by a 20-step bit search): 0 = the default: in a launch with an applied floor,
+ * one count at the floor decides per query set of 32 whether the search runs (no query of the set holds K window rows
+ * at or above the floor: every seed would lose to the floor, so the search is skipped); 1 = always run the search;
+ * 2 = never seed (limits start at the floor, or at minus infinity).  PROCESS-GLOBAL like the knobs above.  All return
+ * the same candidates, and 0 and 1 the same band limits, counters and appends. */
+int fwav_debug_topk_seeds(int mode);
 /* Diagnostic override of the floor's second pass: table pieces per split block of misses (1 … 64; 0 = the default:
  * 64 where the expected misses fill one round of workgroups with them, else as many from 16 to 32 as do).  Re-query
  * fwav_sim_topk_workspace_size afterwards.  All return the same candidates. */

@@ -1,7 +1,8 @@
 """Counters of the fp16 search's first pass (STATS build of the kernel: replayed chunks, firing tiles, appends,
 compactions, time shares) on cfg2 for the first AB_NQ queries (tools only).
 usage: AB_NQ=41344 python tools/first_stats.py   (AB_DBG=262144: the product's geometry instead of the base; 786432: and its floor; AB_RUNS=1: the active
-list in runs of 64 in random order, as fwav_prune leaves it)"""
+list in runs of 64 in random order, as fwav_prune leaves it; AB_SEEDS=m: fwav_debug_topk_seeds(m), 1 = the seeds' bit
+search for every set, 2 = no seeds).  The prologue's counters (dbg 64) are always asked for."""
 import os as _os_dbg
 _os_dbg.environ.setdefault("FWAV_DEBUG_LIBRARY", "1")  # the search knobs: libfwav_debug.so
 import os
@@ -39,6 +40,8 @@ call("fwav_pool_embed", sig.data_ptr(), sig.numel(), 2048, 8, 2, tab.data_ptr(),
      emb16.data_ptr(), ws.data_ptr(), ws.numel(), st)
 if os.environ.get("AB_PLAN"):  # "rt,pieces": the work-plan override (fwav_debug_topk_plan), set before sizing
     call("fwav_debug_topk_plan", *[int(x) for x in os.environ["AB_PLAN"].split(",")])
+if os.environ.get("AB_SEEDS"):
+    call("fwav_debug_topk_seeds", int(os.environ["AB_SEEDS"]))
 nq = int(os.environ.get("AB_NQ", nr))
 active = torch.arange(nq, dtype=torch.int32, device="cuda")
 if os.environ.get("AB_RUNS") == "1":  # fwav_prune's order: runs of 64 consecutive ranges in a random run order
@@ -50,11 +53,11 @@ wsn = size_call("fwav_sim_topk_workspace_size", nq, nd, 64)
 wsk = torch.empty(wsn, dtype=torch.uint8, device="cuda")
 cand = torch.empty(nq * 64, dtype=torch.int32, device="cuda")
 for rep in range(2):
-    stats = torch.zeros(16, dtype=torch.int64, device="cuda")
+    stats = torch.zeros(32, dtype=torch.int64, device="cuda")  # [16 .. 19]: the prologue's counters (dbg 64)
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
     call("fwav_debug_sim_topk", emb.data_ptr(), emb16.data_ptr(), nd, active.data_ptr(), n_active.data_ptr(), nq, 0,
-         64, cand.data_ptr(), wsk.data_ptr(), wsk.numel(), int(os.environ.get("AB_DBG", "0")), stats.data_ptr(), st)
+         64, cand.data_ptr(), wsk.data_ptr(), wsk.numel(), int(os.environ.get("AB_DBG", "0")) | 64, stats.data_ptr(), st)
     e1.record()
     torch.cuda.synchronize()
     sv = stats.cpu().tolist()
@@ -66,4 +69,6 @@ for rep in range(2):
           f"(appends {sv[10] / tot:.3f}, fragment waits {sv[11] / tot:.3f}) final {sv[8] / tot:.3f}; own chunk DMA "
           f"wait {sv[12] / tot:.3f}, compactions {sv[5] / tot:.3f}; centroid: level 1 {sv[13] / tot:.3f}, level-2 pairs "
           f"per query set {sv[14] / qsets:.0f}; busiest wave / mean wave (outside the barrier) "
-          f"{sv[15] * int(os.environ.get('AB_W', 8)) / max(sv[6] - sv[7], 1):.3f}", flush=True)
+          f"{sv[15] * int(os.environ.get('AB_W', 8)) / max(sv[6] - sv[7], 1):.3f}; prologue {sv[16] / tot:.4f} (its seed "
+          f"phase {sv[17] / tot:.4f}), (set, item) pairs that ran the seeds' search {sv[18]}; totals: firing tiles "
+          f"{sv[1]}, appends {sv[2]}, compactions {sv[3]}, level-2 pairs {sv[14]}", flush=True)
