@@ -34,7 +34,8 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
-from .engine import geometry
+from . import geometry, stages
+from ._lib import call, size_call
 
 FIELDS = ("idx", "s", "o", "sym", "err")
 
@@ -94,7 +95,7 @@ def prune_balanced_bounds(ranges: torch.Tensor, n_ranges: int, range_size: int, 
     if world == 1 or n_ranges == 0:
         return [(0, n_ranges)] + [(n_ranges, n_ranges)] * (world - 1)
     x = ranges[:n_ranges * range_size].view(n_ranges, range_size)
-    thr = float(np.float32(energy_thresh * 0.75))
+    thr = stages.prune_thr(energy_thresh)
     active = (x.double().square().mean(dim=1) >= thr).to(torch.int64)
     cs = torch.cumsum(active * 1023 + 1, dim=0)
     # targets total·r // world on the device: one host synchronisation (the cut positions)
@@ -173,9 +174,8 @@ def compress_sharded_start(sig: Optional[torch.Tensor], tile_size: int, top_k: i
     It is validated on every rank before the first collective; a ``compute`` of the caller's own chooses its embedding
     itself, so anything but "matrix" beside one is a ValueError.  ``emb_dim`` (16 or 32, as engine.compress_device)
     likewise: the default compute's embedding width, the same on every rank, 16 beside a compute of the caller's."""
-    from .engine import check_emb_dim, check_embedding
-    check_embedding(embedding, geometry(tile_size)[0])
-    check_emb_dim(emb_dim, embedding)
+    stages.check_embedding(embedding, geometry(tile_size)[0])
+    stages.check_emb_dim(emb_dim, embedding)
     if compute is not None and (embedding != "matrix" or emb_dim != 16):
         raise ValueError("embedding and emb_dim apply to the default compute; a compute of your own passes them to "
                          "compress_device itself")
@@ -338,7 +338,6 @@ def decode_decision(rr: float, dd: float, delta: float, eps: float, beta: float)
 
 
 def decode_span() -> int:
-    from ._lib import size_call
     return size_call("fwav_decode_span")
 
 
@@ -362,14 +361,13 @@ class ShardDecoder:
 
     def __init__(self, idx, s, o, sym, pool, lo, n_ranges_global, range_size, iterations, eps, s_clip=16.0,
                  s_damping=0.0, init: Optional[torch.Tensor] = None):
-        from ._lib import size_call
         self.idx, self.s, self.o, self.sym, self.pool = idx, s, o, sym, pool
         self.init = init  # the rank's reconstruction to start from (None: zeros) — a resumed loop
         self.dev = idx.device
         self.m, self.lo, self.nr, self.rs = int(idx.numel()), int(lo), int(n_ranges_global), int(range_size)
         self.nd = pool.numel() // self.rs
         self.iterations, self.eps = int(iterations), float(eps)
-        self.s_clip, self.s_damping = float(abs(np.float32(s_clip))), float(s_damping)
+        self.s_clip, self.s_damping = stages.clip32(s_clip), float(s_damping)
         ci = size_call("fwav_decode_chunk_iterations")
         self.n_chunks = size_call("fwav_decode_n_chunks", self.iterations, self.eps)
         self.span = size_call("fwav_decode_span")
@@ -389,7 +387,6 @@ class ShardDecoder:
                 self.nr, self.rs, self.pool.data_ptr(), self.nd, self.iterations)
 
     def run(self, chunk: int) -> None:
-        from ._lib import call
         call("fwav_decode_run", *self._common(), chunk, self.eps, self.s_clip, self.s_damping, self._init(),
              self.a.data_ptr(), self.b.data_ptr(), self.partials.data_ptr(), self.state.data_ptr(), self._st())
 
@@ -401,7 +398,6 @@ class ShardDecoder:
         return self.partials[:self.n_prefix]
 
     def reduce(self, chunk: int) -> None:
-        from ._lib import call
         call("fwav_decode_reduce", self.partials.data_ptr(), self.nr, self.rs, self.iterations, chunk, self.eps,
              self.deltas.data_ptr(), self.state.data_ptr(), self._st())
 
@@ -409,7 +405,6 @@ class ShardDecoder:
         """→ (local reconstruction f32[m·rs] device tensor, iterations run, deltas list, pending): pending is None,
         or — stopped for the exact check — the local reconstruction before the last iteration (the result is after
         it)."""
-        from ._lib import call
         if self.iterations == 0 or self.nr == 0:
             return torch.zeros(self.m * self.rs, dtype=torch.float32, device=self.dev), 0, [], None
         call("fwav_decode_finish", *self._common(), self.eps, self.s_clip, self.s_damping, self._init(),
@@ -423,13 +418,12 @@ class ShardDecoder:
     def exact_delta(self, prev: torch.Tensor, nxt: torch.Tensor) -> tuple[float, bool]:
         """Rank 0: the reference's Δ between the whole signal's reconstructions (fwav_decode_exact) and whether it
         stops the loop."""
-        from ._lib import call
         st = torch.tensor([2, 0, 0, 0], dtype=torch.int32, device=self.dev)
         d = torch.zeros(1, dtype=torch.float64, device=self.dev)
         prev = prev.to(self.dev).contiguous()
         nxt = nxt.to(self.dev).contiguous()
-        call("fwav_decode_exact", prev.data_ptr(), nxt.data_ptr(), prev.numel(), self.eps, 0, d.data_ptr(),
-             st.data_ptr(), self._st())
+        stages.decode_exact(prev.data_ptr(), nxt.data_ptr(), prev.numel(), self.eps, 0, d.data_ptr(), st.data_ptr(),
+                            self._st())
         return float(d.item()), int(st[0].item()) == 1
 
     def resumed(self, rec: torch.Tensor, iterations_left: int) -> "ShardDecoder":

@@ -2,7 +2,9 @@
 
 Everything between the input signal and the match arrays stays in HBM and runs on one HIP stream through
 the C-ABI of ``libfwav.so`` (``include/fwav.h``); torch only provides device memory and the stream.  There
-is no CPU fallback: without the library or a device every call raises :class:`~fwav._lib.FwavError`.
+is no CPU fallback: without the library or a device every call raises :class:`~fwav._lib.FwavError`.  This host
+allocates, picks the streams and decides where to synchronise; which entry point serves an embedding mode, a width
+or a query table, and the reference's scalars, are fwav.stages'.
 
 Reference map (``/root/reference/fractal.py``):
   voiced_detection :880-909 + range formation :1074-1112  → fwav_voiced_ranges
@@ -20,26 +22,15 @@ Reference map (``/root/reference/fractal.py``):
 from __future__ import annotations
 
 import dataclasses
-import math
 from typing import Optional
 
-import numpy as np
 import torch
 
-from . import _lib, ties as _ties
+from . import _lib, geometry, stages, ties as _ties  # noqa: F401  geometry: re-exported
 from .nporder import zero_query_candidates  # noqa: F401  (Q11 rows; re-exported)
 from ._lib import FwavError, call, size_call
-
-F32 = np.float32
-#: tie_order → fwav_tie_check's exact_sets argument ("index" never calls it)
-TIE_MODES = {"numpy": 0, "numpy_sets": 1, "numpy_rows": 2, "index": -1}
-
-
-from . import geometry  # noqa: E402,F401  range_size, domain_step (fractal.py:1070-1071)
-
-
-def n_domains_for(n: int, tile_size: int, step: int) -> int:
-    return 0 if n < tile_size else (n - tile_size) // step + 1
+from .stages import (EMB_DIMS, EMBEDDINGS, QUERIES, QUERY_RANGE_MAX_K, TIE_MODES, TIE_REC,  # noqa: F401  re-exported
+                     check_emb_dim, check_embedding, check_query, n_domains_for)
 
 
 def require_device(device=None) -> torch.device:
@@ -60,109 +51,12 @@ def _p(t: Optional[torch.Tensor]) -> Optional[int]:
 _TABLES: dict = {}
 
 
-#: embedding → (tables size call, tables call, pool + embedding call).  "matrix": bit-exact at range sizes 4, 8 and
-#: 16, an f64 matrix DCT elsewhere; "pocketfft": scipy's own DCT sequence, bit-exact at every supported range size
-EMBEDDINGS = {"matrix": ("fwav_embed_tables_size", "fwav_embed_tables", "fwav_pool_embed"),
-              "pocketfft": ("fwav_embed_tables_exact_size", "fwav_embed_tables_exact", "fwav_pool_embed_exact")}
-
-
-def check_embedding(embedding: str, rs: int) -> str:
-    """``embedding`` validated for range size ``rs``: ValueError for an unknown mode, and for "pocketfft" at a range
-    size with no exact plan (there is no silent fall-back to the matrix DCT)."""
-    if embedding not in EMBEDDINGS:
-        raise ValueError(f"embedding must be 'matrix' or 'pocketfft', not {embedding!r}")
-    if embedding == "pocketfft" and not size_call("fwav_embed_exact_supported", int(rs)):
-        raise ValueError(f"embedding='pocketfft' has no exact plan for range size {rs} (supported: 4 to 49 and 50, 54, "
-                         "56, 60, 63, 64); use embedding='matrix'")
-    return embedding
-
-
-#: query → where range i's query vector comes from: domain-embedding row i (the reference's pipeline, quirk Q1) or
-#: the embedding of the range itself (what fractal.py:337-351 computes and the pipeline never calls)
-QUERIES = ("domain_row", "range")
-#: the largest K of the search with a query table of its own (fwav_sim_topk_q)
-QUERY_RANGE_MAX_K = 64
-
-
-def check_query(query: str, emb_dim: int = 16, top_k: int | None = None) -> str:
-    """``query`` validated (no device work): ValueError for a name other than "domain_row" and "range", and for "range"
-    together with emb_dim=32 or top_k > 64 (neither is built)."""
-    if query not in QUERIES:
-        raise ValueError(f"query must be 'domain_row' or 'range', not {query!r}")
-    if query == "range":
-        if emb_dim != 16:
-            raise ValueError("query='range' with emb_dim=32 is out of scope: use emb_dim=16")
-        if top_k is not None and int(top_k) > QUERY_RANGE_MAX_K:
-            raise ValueError(f"query='range' supports top_k <= {QUERY_RANGE_MAX_K}, not {int(top_k)}")
-    return query
-
-
-#: the embedding widths the engine implements (compress_audio's emb_dim): 16, the reference's default, through the
-#: entry points above; 32 through the *_dim entry points of include/fwav.h
-EMB_DIMS = (16, 32)
-
-
-def check_emb_dim(emb_dim, embedding: str = "matrix") -> int:
-    """``emb_dim`` validated: NotImplementedError for a width other than 16 and 32, ValueError for 32 together with
-    embedding="pocketfft" (the exact plans are built for heads of 8 coefficients)."""
-    if emb_dim not in EMB_DIMS:
-        raise NotImplementedError(f"emb_dim={emb_dim!r}: the MI355X engine supports emb_dim 16 and 32")
-    if emb_dim != 16 and embedding == "pocketfft":
-        raise ValueError("embedding='pocketfft' with emb_dim=32 is out of scope: use embedding='matrix'")
-    return int(emb_dim)
-
-
 def embed_tables(rs: int, device: torch.device, embedding: str = "matrix", emb_dim: int = 16) -> torch.Tensor:
-    check_embedding(embedding, rs)
-    dim = check_emb_dim(emb_dim, embedding)
-    key = (rs, dim, str(device), embedding)
+    """stages.embed_tables_host on ``device`` (one copy per range size, width, device and mode)."""
+    key = (rs, emb_dim, str(device), embedding)
     if key not in _TABLES:
-        if dim == 16:
-            size_fn, fill_fn, _ = EMBEDDINGS[embedding]
-            host = np.zeros(size_call(size_fn, rs), np.float64)
-            call(fill_fn, rs, host.ctypes.data)
-        else:
-            host = np.zeros(size_call("fwav_embed_tables_dim_size", rs, dim), np.float64)
-            call("fwav_embed_tables_dim", rs, dim, host.ctypes.data)
-        _TABLES[key] = torch.from_numpy(host).to(device)
+        _TABLES[key] = torch.from_numpy(stages.embed_tables_host(rs, embedding, emb_dim)).to(device)
     return _TABLES[key]
-
-
-def _topk_ws_size(dim: int, mq: int, nd: int, k: int, f16: bool) -> int:
-    """Bytes of the search's workspace for mq queries (fwav_sim_topk / fwav_sim_topk_dim)."""
-    if dim != 16:
-        return size_call("fwav_sim_topk_dim_workspace_size", mq, nd, dim, k)
-    return size_call("fwav_sim_topk_workspace_size", mq, nd, k) if (f16 or k > 64) else 0
-
-
-def _sim_topk(dim, emb, emb16, nd, active_ptr, n_active_ptr, mq, lo, k, threads, cand, ties, wsk, wk, st,
-              xq=None) -> None:
-    """fwav_sim_topk, or fwav_sim_topk_dim on rows of ``dim`` != 16 columns (emb16 then its fp16 table), or with
-    ``xq`` = (qemb, qemb16, n_query_rows, seed_stride) fwav_sim_topk_q."""
-    if xq is not None:
-        qemb, qemb16, nq, stride = xq
-        call("fwav_sim_topk_q", emb.data_ptr(), _p(emb16), nd, qemb.data_ptr(), _p(qemb16), nq, stride, active_ptr,
-             n_active_ptr, mq, lo, k, threads, cand.data_ptr(), _p(ties), wsk.data_ptr(), wk, st)
-    elif dim == 16:
-        call("fwav_sim_topk", emb.data_ptr(), _p(emb16), nd, active_ptr, n_active_ptr, mq, lo, k, threads,
-             cand.data_ptr(), _p(ties), wsk.data_ptr(), wk, st)
-    else:
-        call("fwav_sim_topk_dim", emb.data_ptr(), _p(emb16), nd, dim, active_ptr, n_active_ptr, mq, lo, k, threads,
-             cand.data_ptr(), _p(ties), wsk.data_ptr(), wk, st)
-
-
-def _tie_check(dim, rsh, m, rs, cand, k, pool, nd, emb, lo, threads, ties, max_ties, mode, resolve, st,
-               qemb=None) -> None:
-    """fwav_tie_check, or fwav_tie_check_dim on rows of ``dim`` != 16 columns, or with a query table fwav_tie_check_q."""
-    if qemb is not None:
-        call("fwav_tie_check_q", rsh.data_ptr(), m, rs, cand.data_ptr(), k, pool.data_ptr(), nd, emb.data_ptr(),
-             qemb.data_ptr(), lo, threads, ties.data_ptr(), max_ties, mode, resolve.data_ptr(), st)
-    elif dim == 16:
-        call("fwav_tie_check", rsh.data_ptr(), m, rs, cand.data_ptr(), k, pool.data_ptr(), nd, emb.data_ptr(), lo,
-             threads, ties.data_ptr(), max_ties, mode, resolve.data_ptr(), st)
-    else:
-        call("fwav_tie_check_dim", rsh.data_ptr(), m, rs, cand.data_ptr(), k, pool.data_ptr(), nd, emb.data_ptr(), dim,
-             lo, threads, ties.data_ptr(), max_ties, mode, resolve.data_ptr(), st)
 
 
 _ZERO_CAND_DEV: dict = {}
@@ -231,11 +125,9 @@ class DeviceCompressed:
         return self
 
     def is_silent(self) -> bool:
-        """np.sum((signal·mask)²) < 1e-8 (fractal.py:1083): the device computes numpy's float32 sum bit-exactly, and the
-        comparison is float32 against float32(1e-8) (NEP 50)."""
-        if self.energy_partial is None:
-            return True
-        return bool(F32(self.energy_partial.cpu().numpy()[0]) < F32(1e-8))
+        """np.sum((signal·mask)²) < 1e-8 (fractal.py:1083): the device computes numpy's float32 sum bit-exactly
+        (stages.is_silent)."""
+        return self.energy_partial is None or stages.is_silent(self.energy_partial.cpu().numpy()[0])
 
 
 def _mark(ev, name: str, end: bool = False):
@@ -251,14 +143,14 @@ def _empty(n, rs, tile, step, thr, k) -> DeviceCompressed:
     return DeviceCompressed(0, rs, tile, step, thr, n, 0, k, (0, 0), empty=True)
 
 
-def _voiced_ranges(sig, n, rs, frame, thr32, lo32, st) -> torch.Tensor:
+def _voiced_ranges(sig, n, rs, energy_thresh, st) -> torch.Tensor:
     """fwav_voiced_ranges on the stream ``st``: the voiced-masked, reflect-padded ranges f32[nr·rs]."""
-    nr = -(-n // rs)
+    nr, frame = -(-n // rs), 2 * rs
     ws_n = size_call("fwav_voiced_workspace_size", n, frame)
     ws = torch.empty(ws_n, dtype=torch.uint8, device=sig.device)
     ranges = torch.empty(nr * rs, dtype=torch.float32, device=sig.device)
-    call("fwav_voiced_ranges", sig.data_ptr(), n, rs, frame, 5, float(thr32), float(lo32), ranges.data_ptr(), nr,
-         None, ws.data_ptr(), ws_n, st)
+    call("fwav_voiced_ranges", sig.data_ptr(), n, rs, frame, stages.SMOOTH_WINDOW, stages.voiced_hi(energy_thresh),
+         stages.voiced_lo(energy_thresh), ranges.data_ptr(), nr, None, ws.data_ptr(), ws_n, st)
     return ranges
 
 
@@ -273,7 +165,7 @@ def ranges_device(sig: torch.Tensor, tile_size: int, energy_thresh: float = 1e-4
         rs, _ = geometry(tile_size)
         if n == 0:
             raise ValueError("a cannot be empty")
-        r = _voiced_ranges(sig, n, rs, 2 * rs, F32(energy_thresh), F32(energy_thresh * 0.5), _stream(sig.device))
+        r = _voiced_ranges(sig, n, rs, energy_thresh, _stream(sig.device))
         return r, -(-n // rs), rs
 
 
@@ -336,26 +228,19 @@ def _compress_device(sig: torch.Tensor, tile_size: int, top_k: int, energy_thres
     n = sig.numel()
     k = int(top_k)
     rs, step = geometry(tile_size)
-    frame = 2 * rs
     if n == 0:
         raise ValueError("a cannot be empty")  # np.convolve on zero frames (fractal.py:895)
-    nf = -(-n // frame)
     nr = -(-n // rs)
     nd = n_domains_for(n, tile_size, step)
-    thr32 = F32(energy_thresh)
-    lo32 = F32(energy_thresh * 0.5)
     if k > size_call("fwav_topk_max_k"):
         raise ValueError(f"top_k={k} > {size_call('fwav_topk_max_k')} is not supported by the HIP search")
     check_embedding(embedding, rs)
     dim = check_emb_dim(emb_dim, embedding)
     check_query(query, dim, k)
-    if tie_order not in TIE_MODES:
-        raise ValueError("tie_order must be 'numpy' (the reference's order of exactly tied scores wherever it decides a"
-                         " match), 'numpy_sets' (and wherever it decides a candidate set), 'numpy_rows' (and wherever it"
-                         " decides a candidate row's order) or 'index'")
+    stages.check_tie_order(tie_order)
     threads = _ties.blas_threads() if blas_threads is None else int(blas_threads)
     _mark(events, "voiced_ranges")
-    ranges = _voiced_ranges(sig, n, rs, frame, thr32, lo32, st)
+    ranges = _voiced_ranges(sig, n, rs, energy_thresh, st)
     partial = torch.empty(1, dtype=torch.float32, device=dev)
     wse = size_call("fwav_weighted_energy_workspace_size", n)
     wsen = torch.empty(wse, dtype=torch.uint8, device=dev)
@@ -375,20 +260,12 @@ def _compress_device(sig: torch.Tensor, tile_size: int, top_k: int, energy_thres
         raise ValueError("search must be 'f16' (fp16 pre-filter + exact f32 rescoring) or 'f32'")
     if dim != 16 and search != "f16":
         raise ValueError("search='f32' is not available with emb_dim=32 (the wide search has one kernel)")
-    if dim != 16:
-        emb16 = torch.empty(size_call("fwav_embh_elems", nd, dim), dtype=torch.float16, device=dev)
-    else:
-        emb16 = (torch.empty(2 * ((nd + 255) // 256) * 256 * 16, dtype=torch.float16, device=dev)
-                 if search == "f16" else None)
+    emb16 = (torch.empty(stages.emb16_elems(nd, dim), dtype=torch.float16, device=dev) if search == "f16" else None)
     ws_p = size_call("fwav_pool_workspace_size", n, tile_size, rs, step)
     wsp = torch.empty(max(ws_p, 16), dtype=torch.uint8, device=dev)
     _mark(events, "pool_embed")
-    if dim != 16:
-        call("fwav_pool_embed_dim", sig.data_ptr(), n, tile_size, rs, step, dim, tab.data_ptr(), pool.data_ptr(),
-             emb.data_ptr(), _p(emb16), wsp.data_ptr(), ws_p, st)
-    else:
-        call(EMBEDDINGS[embedding][2], sig.data_ptr(), n, tile_size, rs, step, tab.data_ptr(), pool.data_ptr(),
-             emb.data_ptr(), _p(emb16), wsp.data_ptr(), ws_p, st)
+    stages.pool_embed(sig.data_ptr(), n, tile_size, rs, step, tab.data_ptr(), pool.data_ptr(), emb.data_ptr(),
+                      _p(emb16), wsp.data_ptr(), ws_p, st, embedding=embedding, emb_dim=dim)
     _mark(events, "pool_embed")
     if on_pool is not None:
         on_pool(pool)
@@ -397,10 +274,9 @@ def _compress_device(sig: torch.Tensor, tile_size: int, top_k: int, energy_thres
         # every range's own embedding, by the pool rows' kernel (the whole signal's: a shard's queries are rows lo … hi)
         _mark(events, "embed_rows")
         qemb = torch.empty(nr * 16, dtype=torch.float32, device=dev)
-        qemb16 = (torch.empty(size_call("fwav_emb16_elems", nr), dtype=torch.float16, device=dev)
-                  if emb16 is not None else None)
-        call("fwav_embed_rows_exact" if embedding == "pocketfft" else "fwav_embed_rows", ranges.data_ptr(), nr, rs,
-             tab.data_ptr(), qemb.data_ptr(), _p(qemb16), st)
+        qemb16 = (torch.empty(stages.emb16_elems(nr), dtype=torch.float16, device=dev) if emb16 is not None else None)
+        stages.embed_rows(ranges.data_ptr(), nr, rs, tab.data_ptr(), qemb.data_ptr(), _p(qemb16), st,
+                          embedding=embedding)
         _mark(events, "embed_rows")
         # the first pass seeds range i's limit around the domain whose window starts where the range does
         xq = (qemb, qemb16, nr, rs // step)
@@ -423,19 +299,14 @@ def _compress_device(sig: torch.Tensor, tile_size: int, top_k: int, energy_thres
     sym = torch.empty(m, dtype=torch.uint8, device=dev)
     err = torch.empty(m, dtype=torch.float32, device=dev)
     if m > 0:
+        S = _Search(emb, emb16, nd, dim, xq, lo, k, threads, rs, rsh, pool, cand, (idx, s, o, sym, err),
+                    stages.clip32(s_clip), TIE_MODES[tie_order])
         _mark(events, "prune")
         zc = _zero_cand_device(nd, k, dev)
-        if qemb is not None:
-            call("fwav_prune_q", rsh.data_ptr(), m, lo, rs, float(F32(energy_thresh * 0.75)), int(bool(fast_mode)),
-                 qemb.data_ptr(), nr, nd, k, zc.data_ptr(), cand.data_ptr(), active.data_ptr(), n_active.data_ptr(), st)
-        elif dim != 16:
-            call("fwav_prune_dim", rsh.data_ptr(), m, lo, rs, float(F32(energy_thresh * 0.75)), int(bool(fast_mode)),
-                 emb.data_ptr(), nd, dim, k, zc.data_ptr(), cand.data_ptr(), active.data_ptr(), n_active.data_ptr(), st)
-        else:
-            call("fwav_prune", rsh.data_ptr(), m, lo, rs, float(F32(energy_thresh * 0.75)), int(bool(fast_mode)),
-                 emb.data_ptr(), nd, k, zc.data_ptr(), cand.data_ptr(), active.data_ptr(), n_active.data_ptr(), st)
+        stages.prune(rsh.data_ptr(), m, lo, rs, stages.prune_thr(energy_thresh), int(bool(fast_mode)), emb.data_ptr(),
+                     nd, k, zc.data_ptr(), cand.data_ptr(), active.data_ptr(), n_active.data_ptr(), st, emb_dim=dim,
+                     qemb=_p(qemb), n_query_rows=nr)
         _mark(events, "prune")
-        sc = float(abs(F32(s_clip)))
         nsub = 1
         sliced = False
         if tie_order != "index":
@@ -450,49 +321,43 @@ def _compress_device(sig: torch.Tensor, tile_size: int, top_k: int, energy_thres
             sliced = nsub > 1 or (defer_ties and nd >= SUB_BLOCK_MIN_DOMAINS)
         if not sliced:
             _mark(events, "sim_topk")
-            wk = _topk_ws_size(dim, m, nd, k, emb16 is not None)
+            wk = S.workspace_size(m)
             wsk = torch.empty(max(wk, 16), dtype=torch.uint8, device=dev)
             ties = (torch.empty(size_call("fwav_tie_list_size", m), dtype=torch.int32, device=dev)
                     if tie_order != "index" else None)
-            _sim_topk(dim, emb, emb16, nd, active.data_ptr(), n_active.data_ptr(), m, lo, k, threads, cand, ties, wsk,
-                      wk, st, xq)
+            S.sim_topk(active.data_ptr(), n_active.data_ptr(), m, ties, wsk, wk, st)
             _mark(events, "sim_topk")
             _mark(events, "affine")
-            call("fwav_affine", rsh.data_ptr(), m, rs, cand.data_ptr(), k, pool.data_ptr(), nd, sc, idx.data_ptr(),
-                 s.data_ptr(), o.data_ptr(), sym.data_ptr(), err.data_ptr(), st)
+            S.affine(m, st)
             _mark(events, "affine")
         if not sliced and ties is not None:
             # exactly tied scores whose order can change a match: numpy's own ranking for those rows (fwav.ties)
             _mark(events, "ties")
             resolve = torch.empty(m + 1, dtype=torch.int32, device=dev)
-            _tie_check(dim, rsh, m, rs, cand, k, pool, nd, emb, lo, threads, ties, m, TIE_MODES[tie_order], resolve, st,
-                       qemb)
+            S.tie_check(m, ties, m, resolve, st)
+
+            def counts():
+                c = torch.stack([ties[0], resolve[0]]).cpu()
+                res.n_ties, res.n_resolved = int(c[0]), int(c[1])
+                return resolve[1:1 + res.n_resolved]
 
             def finish(stream_id):
-                counts = torch.stack([ties[0], resolve[0]]).cpu()
-                res.n_ties, res.n_resolved = int(counts[0]), int(counts[1])
+                rows = counts()
                 if res.n_resolved:
-                    _ties.resolve_rows(resolve[1:1 + res.n_resolved], emb=emb, n_domains=nd, q_offset=lo, k=k,
-                                       threads=threads, emb_dim=dim, ranges=rsh, range_size=rs, pool=pool, s_clip=sc, cand=cand,
-                                       outs=(idx, s, o, sym, err), stream=stream_id, qemb=qemb)
+                    _ties.resolve_rows(rows, stream=stream_id, **S.rows_kw, **S.fix_kw)
 
             def stage(stream_id):
                 # deferred: on the driver thread, the counts, the exact score rows and their copies; numpy's ranking
                 # then runs on the host pool while the driver moves on to the next call, and wait() applies it
-                counts = torch.stack([ties[0], resolve[0]]).cpu()
-                res.n_ties, res.n_resolved = int(counts[0]), int(counts[1])
+                rows = counts()
                 if not res.n_resolved:
                     return None
-                rows = resolve[1:1 + res.n_resolved]
-                futs = _ties.rank_rows(_ties.score_row_launches(rows, emb=emb, n_domains=nd, q_offset=lo,
-                                                                threads=threads, stream=stream_id, emb_dim=dim,
-                                                                qemb=qemb),
-                                       res.n_resolved, nd, k)
+                futs = _ties.rank_rows(_ties.score_row_launches(rows, stream=stream_id, **S.rows_kw), res.n_resolved,
+                                       nd, k)
                 return rows, futs
 
             def apply(rows, futs):
-                _ties.apply_rows(rows, futs, ranges=rsh, range_size=rs, pool=pool, n_domains=nd, k=k, s_clip=sc,
-                                 cand=cand, outs=(idx, s, o, sym, err), stream=_stream(dev))
+                _ties.apply_rows(rows, futs, n_domains=nd, stream=_stream(dev), **S.fix_kw)
 
             if defer_ties:
                 res.apply = apply
@@ -503,9 +368,7 @@ def _compress_device(sig: torch.Tensor, tile_size: int, top_k: int, energy_thres
                     res.resolved = resolve[1:1 + res.n_resolved]
             _mark(events, "ties")
         elif sliced:
-            ties = _search_sub_blocks(nsub, m, nd, k, lo, rs, threads, sc, tie_order, emb, emb16, active, n_active,
-                                      rsh, pool, cand, (idx, s, o, sym, err), res, events, st, defer=defer_ties,
-                                      dim=dim, xq=xq)
+            ties = _search_sub_blocks(S, nsub, m, active, n_active, res, events, st, defer_ties)
     res.pool, res.idx, res.s, res.o, res.sym, res.err, res.n_active = pool, idx, s, o, sym, err, n_active
     if keep_intermediates:
         res.ranges, res.emb, res.cand, res.active, res.qemb = ranges, emb, cand, active, qemb
@@ -516,12 +379,68 @@ def _compress_device(sig: torch.Tensor, tile_size: int, top_k: int, energy_thres
     return res
 
 
+@dataclasses.dataclass
+class _Search:
+    """What the search stages of one call share, bound once: the tables (``query``: None, or query="range"'s
+    (qemb, qemb16, n_query_rows, seed_stride)), the shard [lo, lo + m) with its ranges, candidates and outputs
+    ``outs`` = (idx, s, o, sym, err), and ``tie_mode`` = TIE_MODES[tie_order]."""
+
+    emb: torch.Tensor
+    emb16: Optional[torch.Tensor]
+    nd: int
+    dim: int
+    query: Optional[tuple]
+    lo: int
+    k: int
+    threads: int
+    rs: int
+    rsh: torch.Tensor
+    pool: torch.Tensor
+    cand: torch.Tensor
+    outs: tuple
+    s_clip: float
+    tie_mode: int
+
+    @property
+    def qemb(self) -> Optional[torch.Tensor]:
+        return None if self.query is None else self.query[0]
+
+    @property
+    def rows_kw(self) -> dict:
+        """The keywords of fwav.ties' exact score rows (score_row_launches, rank_rows_async, resolve_rows)."""
+        return dict(emb=self.emb, n_domains=self.nd, q_offset=self.lo, threads=self.threads, emb_dim=self.dim,
+                    qemb=self.qemb)
+
+    @property
+    def fix_kw(self) -> dict:
+        """... and of its fix-up (apply_rows, resolve_rows)."""
+        return dict(ranges=self.rsh, range_size=self.rs, pool=self.pool, k=self.k, s_clip=self.s_clip, cand=self.cand,
+                    outs=self.outs)
+
+    def workspace_size(self, mq: int) -> int:
+        return stages.topk_workspace_size(mq, self.nd, self.k, emb_dim=self.dim, f16=self.emb16 is not None)
+
+    def sim_topk(self, active_ptr, n_active_ptr, mq, ties, wsk, wk, st) -> None:
+        q = self.query
+        stages.sim_topk(self.emb.data_ptr(), _p(self.emb16), self.nd, active_ptr, n_active_ptr, mq, self.lo, self.k,
+                        self.threads, self.cand.data_ptr(), _p(ties), wsk.data_ptr(), wk, st, emb_dim=self.dim,
+                        query=None if q is None else (q[0].data_ptr(), _p(q[1]), q[2], q[3]))
+
+    def affine(self, m, st) -> None:
+        call("fwav_affine", self.rsh.data_ptr(), m, self.rs, self.cand.data_ptr(), self.k, self.pool.data_ptr(), self.nd,
+             self.s_clip, *[t.data_ptr() for t in self.outs], st)
+
+    def tie_check(self, m, ties, max_ties, resolve, st) -> None:
+        stages.tie_check(self.rsh.data_ptr(), m, self.rs, self.cand.data_ptr(), self.k, self.pool.data_ptr(), self.nd,
+                         self.emb.data_ptr(), self.lo, self.threads, ties.data_ptr(), max_ties, self.tie_mode,
+                         resolve.data_ptr(), st, emb_dim=self.dim, qemb=_p(self.qemb))
+
+
 #: query sub-blocks of a search whose tied rows are ranked while the next sub-block searches: only where numpy's
 #: ranking of a row is expensive (tables of ≥ 4 Mi domains: a cfg3 row 13 ms, a cfg4 row ≈ 50 ms on the host) and
 #: every sub-block still fills the chip for a few rounds (≥ 400,000 queries; a slice launch costs ≈ 26 ms more at
 #: cfg3, 60 ms at cfg4: profiles/r03/sub_blocks_cfg3.log, sub_blocks_cfg4_eighth.log)
 SUB_BLOCK_MIN_DOMAINS = 1 << 22
-TIE_REC = 9  # int32 per tie record (kTieRec, fwav_common.h)
 SUB_BLOCK_QUERIES = 400_000
 
 
@@ -550,17 +469,15 @@ class _Staged:
         return (self.pend,)
 
 
-def _search_sub_blocks(nsub, m, nd, k, lo, rs, threads, sc, tie_order, emb, emb16, active, n_active, rsh, pool, cand,
-                       outs, res, events, st, defer=False, dim=16, xq=None):
+def _search_sub_blocks(S: _Search, nsub, m, active, n_active, res, events, st, defer=False):
     """The search as ``nsub`` launches over consecutive slices of the active list.  After each slice's search and tie
     check the host reads its tie counts (one synchronisation), queues the exact score rows of its tied rows and hands
     their copies and numpy's ranking to the driver thread (fwav.ties.rank_rows_async); then the next slice searches.
     The affine solve runs once over the shard after the last slice, then the ranked rows are applied.  Returns the
-    slices' tie records as one list.  ``xq``: the query table of a query="range" search (_sim_topk)."""
-    dev = rsh.device
-    qemb = None if xq is None else xq[0]
+    slices' tie records as one list."""
+    dev = S.rsh.device
     bounds = _slice_bounds(m, nsub)
-    wk = max(_topk_ws_size(dim, b - a, nd, k, emb16 is not None) for a, b in bounds)
+    wk = max(S.workspace_size(b - a) for a, b in bounds)
     wsk = torch.empty(max(wk, 16), dtype=torch.uint8, device=dev)
     pend = []
     lists = []  # each slice's tie records
@@ -570,11 +487,9 @@ def _search_sub_blocks(nsub, m, nd, k, lo, rs, threads, sc, tie_order, emb, emb1
         mq = j1 - j0
         na = torch.clamp(n_active - j0, 0, mq).to(torch.int32)
         ties = torch.empty(size_call("fwav_tie_list_size", mq), dtype=torch.int32, device=dev)
-        _sim_topk(dim, emb, emb16, nd, active[j0:].data_ptr(), na.data_ptr(), mq, lo, k, threads, cand, ties, wsk, wk, st,
-                  xq)
+        S.sim_topk(active[j0:].data_ptr(), na.data_ptr(), mq, ties, wsk, wk, st)
         resolve = torch.empty(mq + 1, dtype=torch.int32, device=dev)
-        _tie_check(dim, rsh, m, rs, cand, k, pool, nd, emb, lo, threads, ties, mq, TIE_MODES[tie_order], resolve, st,
-                   qemb)
+        S.tie_check(m, ties, mq, resolve, st)
         counts = torch.stack([ties[0], resolve[0]]).cpu()
         if _ties._TRACE:
             import time
@@ -586,17 +501,15 @@ def _search_sub_blocks(nsub, m, nd, k, lo, rs, threads, sc, tie_order, emb, emb1
         n_res += nr_j
         if nr_j:
             rows = resolve[1:1 + nr_j]
-            pend.append((rows, _ties.rank_rows_async(rows, emb=emb, n_domains=nd, q_offset=lo, k=k, threads=threads,
-                                                     stream=st, emb_dim=dim, qemb=qemb)))
+            pend.append((rows, _ties.rank_rows_async(rows, k=S.k, stream=st, **S.rows_kw)))
     _mark(events, "sim_topk")
     _mark(events, "affine")
-    call("fwav_affine", rsh.data_ptr(), m, rs, cand.data_ptr(), k, pool.data_ptr(), nd, sc, *[t.data_ptr() for t in outs],
-         st)
+    S.affine(m, st)
     _mark(events, "affine")
+
     def apply(pend_):
         for rows, fut in pend_:
-            _ties.apply_rows(rows, fut.result(), ranges=rsh, range_size=rs, pool=pool, n_domains=nd, k=k, s_clip=sc,
-                             cand=cand, outs=outs, stream=_stream(dev))
+            _ties.apply_rows(rows, fut.result(), n_domains=S.nd, stream=_stream(dev), **S.fix_kw)
 
     res.n_ties, res.n_resolved = n_ties, n_res
     res.resolved = torch.cat([r for r, _ in pend]) if pend else torch.empty(0, dtype=torch.int32, device=dev)
@@ -624,7 +537,7 @@ def compact_arrays(idx: torch.Tensor, pool: torch.Tensor, n_domains: int, range_
         raise ValueError("pool holds fewer than n_domains rows")
     with torch.cuda.device(dev):
         idx, pool = idx.contiguous(), pool.contiguous()
-        cap = min(nd, max(nr, 1))
+        cap = stages.compact_rows_cap(nd, nr)
         idx_out = torch.empty(nr, dtype=torch.int32, device=dev)
         pool_out = torch.empty(cap * rs, dtype=torch.float32, device=dev)
         kept = torch.empty(cap, dtype=torch.int32, device=dev)
@@ -633,9 +546,7 @@ def compact_arrays(idx: torch.Tensor, pool: torch.Tensor, n_domains: int, range_
         ws = torch.empty(wsn, dtype=torch.uint8, device=dev)
         call("fwav_compact_domains", idx.data_ptr(), nr, pool.data_ptr(), nd, rs, idx_out.data_ptr(),
              pool_out.data_ptr(), kept.data_ptr(), counts.data_ptr(), ws.data_ptr(), wsn, _stream(dev))
-        m, over = (int(v) for v in counts.cpu())
-    if over:
-        raise IndexError("domain index out of range")
+        m = stages.compact_count(counts.cpu())
     return idx_out, pool_out[:m * rs], kept[:m], m
 
 
@@ -681,23 +592,17 @@ def _decompress_device(idx: torch.Tensor, s: torch.Tensor, o: torch.Tensor, sym:
     state = torch.zeros(4, dtype=torch.int32, device=dev)
     wsn = size_call("fwav_decode_workspace_size", nr, rs, it)
     ws = torch.empty(max(wsn, 16), dtype=torch.uint8, device=dev)
-    done, init, out = 0, None, a
-    while True:
-        call("fwav_decode_from", idx.data_ptr(), s.data_ptr(), o.data_ptr(), sym.data_ptr(), nr, rs, pool.data_ptr(),
-             nd, it - done, eps, float(abs(F32(s_clip))), float(s_damping), _p(init), a.data_ptr(), b.data_ptr(),
-             deltas[done:].data_ptr(), state.data_ptr(), ws.data_ptr(), wsn, st)
-        stt = state.cpu().numpy()
-        ran = int(stt[1])
-        out, other = (b, a) if int(stt[2]) == 1 else (a, b)
-        if int(stt[0]) == 2:  # the reference's Δ decides: computed in its own sdot order
-            call("fwav_decode_exact", other.data_ptr(), out.data_ptr(), nr * rs, eps, ran - 1,
-                 deltas[done:].data_ptr(), state.data_ptr(), st)
-            if int(state[0].item()) == 3 and done + ran < it:  # it goes on: resume from this reconstruction
-                init = out.clone()
-                done += ran
-                continue
-        done += ran
-        break
+    kept = []  # the reconstruction a resumed loop starts from
+
+    def snapshot(ptr):
+        kept[:] = [(a if ptr == a.data_ptr() else b).clone()]
+        return kept[0].data_ptr()
+
+    in_b, done = stages.decode(idx.data_ptr(), s.data_ptr(), o.data_ptr(), sym.data_ptr(), nr, rs, pool.data_ptr(), nd, it,
+                               eps, stages.clip32(s_clip), float(s_damping), a.data_ptr(), b.data_ptr(),
+                               deltas.data_ptr(), state.data_ptr(), ws.data_ptr(), wsn, st,
+                               read_state=lambda: state.cpu().numpy(), snapshot=snapshot)
+    out = b if in_b else a
     if nr == 0:
         out = a[:0]
     return out[:nr * rs], done, deltas.cpu().numpy()[:done].tolist()

@@ -4,7 +4,8 @@ This is the binding a maintainer of the reference would add to ``fractal.py`` (I
 numpy arrays out, libfwav's C ABI in between, nothing from PyTorch (importing this module imports no torch).  The
 product host (fwav.engine) uses torch tensors only as device buffers; :func:`compress` and :func:`decompress` drive
 the whole device sequence of INTEGRATION.md §2.3 with HIP buffers alone — the cpu_worker / _process_gpu_batch
-pipeline of compress_audio (fractal.py:1040-1256, :556-632, :757-870) and decompress_audio (:1378-1473).
+pipeline of compress_audio (fractal.py:1040-1256, :556-632, :757-870) and decompress_audio (:1378-1473).  The table
+from (embedding, width) to entry point is fwav.stages (torch-free too); this module is the example that calls it.
 """
 from __future__ import annotations
 
@@ -13,8 +14,7 @@ import sys
 
 import numpy as np
 
-from . import geometry
-from . import _lib
+from . import _lib, geometry, stages
 from ._lib import FwavError, call, size_call
 from .nporder import blas_threads, numpy_topk_row, zero_query_candidates
 
@@ -115,30 +115,11 @@ def affine_batch(ranges: np.ndarray, cand: np.ndarray, pool: np.ndarray, s_clip:
     nd = pool.shape[0]
     dr, dc, dp = (DeviceBuffer.from_array(x) for x in (ranges, cand, pool))
     outs = [DeviceBuffer(4 * B), DeviceBuffer(4 * B), DeviceBuffer(4 * B), DeviceBuffer(B), DeviceBuffer(4 * B)]
-    call("fwav_affine", dr.value, B, rs, dc.value, K, dp.value, nd, float(abs(np.float32(s_clip))),
+    call("fwav_affine", dr.value, B, rs, dc.value, K, dp.value, nd, stages.clip32(s_clip),
          *[b.value for b in outs], None)
     call("fwav_stream_sync", None)
     return (outs[0].to_array(np.int32, B), outs[1].to_array(np.float32, B), outs[2].to_array(np.float32, B),
             outs[3].to_array(np.uint8, B), outs[4].to_array(np.float32, B))
-
-
-#: embedding → (tables size call, tables call, pool + embedding call), as fwav.engine.EMBEDDINGS
-EMBEDDINGS = {"matrix": ("fwav_embed_tables_size", "fwav_embed_tables", "fwav_pool_embed"),
-              "pocketfft": ("fwav_embed_tables_exact_size", "fwav_embed_tables_exact", "fwav_pool_embed_exact")}
-
-
-def _embed_tables(rs: int, embedding: str) -> np.ndarray:
-    """The host table of the embedding mode; ValueError for an unknown mode and for "pocketfft" at a range size with
-    no exact plan (no fall-back to the matrix DCT)."""
-    if embedding not in EMBEDDINGS:
-        raise ValueError(f"embedding must be 'matrix' or 'pocketfft', not {embedding!r}")
-    if embedding == "pocketfft" and not size_call("fwav_embed_exact_supported", int(rs)):
-        raise ValueError(f"embedding='pocketfft' has no exact plan for range size {rs} (supported: 4 to 49 and 50, 54, "
-                         "56, 60, 63, 64); use embedding='matrix'")
-    size_fn, fill_fn, _ = EMBEDDINGS[embedding]
-    tab = np.empty(size_call(size_fn, rs), np.float64)
-    call(fill_fn, rs, tab.ctypes.data)
-    return tab
 
 
 def pool_embed(signal: np.ndarray, tile: int, rs: int, step: int, embedding: str = "matrix"):
@@ -147,13 +128,13 @@ def pool_embed(signal: np.ndarray, tile: int, rs: int, step: int, embedding: str
     sig = np.ascontiguousarray(signal, np.float32)
     n = sig.size
     nd = (n - tile) // step + 1
-    tab = _embed_tables(rs, embedding)
+    tab = stages.embed_tables_host(rs, embedding)
     ds, dt = DeviceBuffer.from_array(sig), DeviceBuffer.from_array(tab)
     dpool, demb = DeviceBuffer(4 * nd * rs), DeviceBuffer(4 * nd * 16)
     wsn = size_call("fwav_pool_workspace_size", n, tile, rs, step)
     dws = DeviceBuffer(wsn)
-    call(EMBEDDINGS[embedding][2], ds.value, n, tile, rs, step, dt.value, dpool.value, demb.value, None, dws.value,
-         wsn, None)
+    stages.pool_embed(ds.value, n, tile, rs, step, dt.value, dpool.value, demb.value, None, dws.value, wsn, None,
+                      embedding=embedding)
     call("fwav_stream_sync", None)
     return dpool.to_array(np.float32, nd * rs).reshape(nd, rs), demb.to_array(np.float32, nd * 16).reshape(nd, 16)
 
@@ -177,46 +158,36 @@ def compress(signal: np.ndarray, tile_size: int, top_k: int, energy_thresh: floa
     domain_step, n_domains, n_ties, n_resolved.  ``tie_order`` as fwav.engine.compress_device ("numpy",
     "numpy_sets", "numpy_rows" or "index"), ``embedding`` too: "matrix" (fwav_pool_embed) or "pocketfft"
     (fwav_pool_embed_exact: scipy's DCT sequence at every supported range size, ValueError at the others).
-    ``emb_dim=32`` runs the same sequence through the ``*_dim`` entry points (fwav_pool_embed_dim, fwav_prune_dim,
-    fwav_sim_topk_dim, fwav_tie_check_dim, fwav_score_rows_dim) on rows of 32 columns (emb f32[nd, 32]); it needs
-    embedding="matrix" (ValueError otherwise), and any width but 16 and 32 is NotImplementedError.
+    ``emb_dim=32`` runs the same sequence through the ``*_dim`` entry points on rows of 32 columns (emb f32[nd, 32]);
+    it needs embedding="matrix" (ValueError otherwise), and any width but 16 and 32 is NotImplementedError.  Each stage
+    below is one call of fwav.stages, which picks the entry point of the mode and width and holds the reference's
+    scalars (the voiced thresholds, the prune threshold, the silent test).
     ``compact=True`` ends the sequence with fwav_compact_domains: ``pool`` then holds only the m rows that the matches
     name (f32[m, rs], ascending original index), ``idx`` is renumbered to them, ``n_domains`` = m, and ``kept``
     i32[m] gives each row's original index (``emb`` and ``cand`` keep the original numbering)."""
-    if emb_dim not in (16, 32):
-        raise NotImplementedError(f"emb_dim={emb_dim!r}: the MI355X engine supports emb_dim 16 and 32")
-    if emb_dim != 16 and embedding == "pocketfft":
-        raise ValueError("embedding='pocketfft' with emb_dim=32 is out of scope: use embedding='matrix'")
-    dim, wide = int(emb_dim), emb_dim != 16
-    modes = {"numpy": 0, "numpy_sets": 1, "numpy_rows": 2, "index": -1}  # → fwav_tie_check's exact_sets
-    if tie_order not in modes:
-        raise ValueError("tie_order must be 'numpy', 'numpy_sets', 'numpy_rows' or 'index'")
+    dim = stages.check_emb_dim(emb_dim, embedding)
+    stages.check_tie_order(tie_order)
     sig = np.ascontiguousarray(signal, np.float32).reshape(-1)
     n = sig.size
     if n == 0:
         raise ValueError("a cannot be empty")  # np.convolve on zero frames (fractal.py:895)
     k = int(top_k)
     rs, step = geometry(tile_size)
-    if wide:
-        tab = np.empty(size_call("fwav_embed_tables_dim_size", rs, dim), np.float64)
-        call("fwav_embed_tables_dim", rs, dim, tab.ctypes.data)
-    else:
-        tab = _embed_tables(rs, embedding)
+    tab = stages.embed_tables_host(rs, embedding, dim)
     frame = 2 * rs
     nr = -(-n // rs)
-    nd = 0 if n < tile_size else (n - tile_size) // step + 1
+    nd = stages.n_domains_for(n, tile_size, step)
     T = blas_threads() if threads is None else int(threads)
-    thr32, lo32 = np.float32(energy_thresh), np.float32(energy_thresh * 0.5)
     d_sig = DeviceBuffer.from_array(sig)
     d_ranges = DeviceBuffer(4 * nr * rs)
     wsv = size_call("fwav_voiced_workspace_size", n, frame)
     d_wsv = DeviceBuffer(wsv)
-    call("fwav_voiced_ranges", d_sig.value, n, rs, frame, 5, float(thr32), float(lo32), d_ranges.value, nr, None,
-         d_wsv.value, wsv, None)
+    call("fwav_voiced_ranges", d_sig.value, n, rs, frame, stages.SMOOTH_WINDOW, stages.voiced_hi(energy_thresh),
+         stages.voiced_lo(energy_thresh), d_ranges.value, nr, None, d_wsv.value, wsv, None)
     wse = size_call("fwav_weighted_energy_workspace_size", n)
     d_wse, d_part = DeviceBuffer(wse), DeviceBuffer(4)
     call("fwav_weighted_energy", d_ranges.value, n, d_part.value, d_wse.value, wse, None)
-    silent = np.float32(d_part.to_array(np.float32, 1)[0]) < np.float32(1e-8)
+    silent = stages.is_silent(d_part.to_array(np.float32, 1)[0])
     if n < tile_size or nr > nd:
         if silent or n < tile_size:
             return None
@@ -225,44 +196,28 @@ def compress(signal: np.ndarray, tile_size: int, top_k: int, energy_thresh: floa
         return None
     d_tab = DeviceBuffer.from_array(tab)
     d_pool, d_emb = DeviceBuffer(4 * nd * rs), DeviceBuffer(4 * nd * dim)
-    d_emb16 = DeviceBuffer(2 * (size_call("fwav_embh_elems", nd, dim) if wide else size_call("fwav_emb16_elems", nd)))
+    d_emb16 = DeviceBuffer(2 * stages.emb16_elems(nd, dim))
     wsp = size_call("fwav_pool_workspace_size", n, tile_size, rs, step)
     d_wsp = DeviceBuffer(wsp)
-    if wide:
-        call("fwav_pool_embed_dim", d_sig.value, n, tile_size, rs, step, dim, d_tab.value, d_pool.value, d_emb.value,
-             d_emb16.value, d_wsp.value, wsp, None)
-    else:
-        call(EMBEDDINGS[embedding][2], d_sig.value, n, tile_size, rs, step, d_tab.value, d_pool.value, d_emb.value,
-             d_emb16.value, d_wsp.value, wsp, None)
+    stages.pool_embed(d_sig.value, n, tile_size, rs, step, d_tab.value, d_pool.value, d_emb.value, d_emb16.value,
+                      d_wsp.value, wsp, None, embedding=embedding, emb_dim=dim)
     d_cand, d_active, d_nact = DeviceBuffer(4 * nr * k), DeviceBuffer(4 * nr), DeviceBuffer(4)
     d_zc = DeviceBuffer.from_array(zero_query_candidates(nd, k))
     d_ties = DeviceBuffer(4 * size_call("fwav_tie_list_size", nr))
-    if wide:
-        call("fwav_prune_dim", d_ranges.value, nr, 0, rs, float(np.float32(energy_thresh * 0.75)),
-             int(bool(fast_mode)), d_emb.value, nd, dim, k, d_zc.value, d_cand.value, d_active.value, d_nact.value, None)
-        wsk = size_call("fwav_sim_topk_dim_workspace_size", nr, nd, dim, k)
-        d_wsk = DeviceBuffer(wsk)
-        call("fwav_sim_topk_dim", d_emb.value, d_emb16.value, nd, dim, d_active.value, d_nact.value, nr, 0, k, T,
-             d_cand.value, d_ties.value, d_wsk.value, wsk, None)
-    else:
-        call("fwav_prune", d_ranges.value, nr, 0, rs, float(np.float32(energy_thresh * 0.75)), int(bool(fast_mode)),
-             d_emb.value, nd, k, d_zc.value, d_cand.value, d_active.value, d_nact.value, None)
-        wsk = size_call("fwav_sim_topk_workspace_size", nr, nd, k)
-        d_wsk = DeviceBuffer(wsk)
-        call("fwav_sim_topk", d_emb.value, d_emb16.value, nd, d_active.value, d_nact.value, nr, 0, k, T, d_cand.value,
-             d_ties.value, d_wsk.value, wsk, None)
+    stages.prune(d_ranges.value, nr, 0, rs, stages.prune_thr(energy_thresh), int(bool(fast_mode)), d_emb.value, nd, k,
+                 d_zc.value, d_cand.value, d_active.value, d_nact.value, None, emb_dim=dim)
+    wsk = stages.topk_workspace_size(nr, nd, k, emb_dim=dim)
+    d_wsk = DeviceBuffer(wsk)
+    stages.sim_topk(d_emb.value, d_emb16.value, nd, d_active.value, d_nact.value, nr, 0, k, T, d_cand.value,
+                    d_ties.value, d_wsk.value, wsk, None, emb_dim=dim)
     outs = [DeviceBuffer(4 * nr), DeviceBuffer(4 * nr), DeviceBuffer(4 * nr), DeviceBuffer(nr), DeviceBuffer(4 * nr)]
-    sc = float(abs(np.float32(s_clip)))
+    sc = stages.clip32(s_clip)
     call("fwav_affine", d_ranges.value, nr, rs, d_cand.value, k, d_pool.value, nd, sc, *[b.value for b in outs], None)
     n_ties = n_res = 0
     if tie_order != "index":
         d_res = DeviceBuffer(4 * (nr + 1))
-        if wide:
-            call("fwav_tie_check_dim", d_ranges.value, nr, rs, d_cand.value, k, d_pool.value, nd, d_emb.value, dim, 0,
-                 T, d_ties.value, nr, modes[tie_order], d_res.value, None)
-        else:
-            call("fwav_tie_check", d_ranges.value, nr, rs, d_cand.value, k, d_pool.value, nd, d_emb.value, 0, T,
-                 d_ties.value, nr, modes[tie_order], d_res.value, None)
+        stages.tie_check(d_ranges.value, nr, rs, d_cand.value, k, d_pool.value, nd, d_emb.value, 0, T, d_ties.value, nr,
+                         stages.TIE_MODES[tie_order], d_res.value, None, emb_dim=dim)
         n_ties = int(_i32(d_ties, 1)[0])
         res = _i32(d_res, 1 + nr)
         n_res = int(res[0])
@@ -273,33 +228,25 @@ def compress(signal: np.ndarray, tile_size: int, top_k: int, energy_thresh: floa
             d_sr = DeviceBuffer(4 * nd)
             newc = np.empty((n_res, k), np.int32)
             for j in range(n_res):
-                if wide:
-                    call("fwav_score_rows_dim", d_emb.value, nd, dim, d_rows.value + 4 * j, 1, 0, T, d_sr.value, None)
-                else:
-                    call("fwav_score_rows", d_emb.value, nd, d_rows.value + 4 * j, 1, 0, T, d_sr.value, None)
+                stages.score_rows(d_emb.value, nd, d_rows.value + 4 * j, 1, 0, T, d_sr.value, None, emb_dim=dim)
                 newc[j] = numpy_topk_row(d_sr.to_array(np.float32, nd), k)
             d_newc = DeviceBuffer.from_array(newc)
             d_rsub = DeviceBuffer(4 * n_res * rs)
-            call("fwav_tie_rows_in", d_rows.value, n_res, d_newc.value, k, d_cand.value, d_ranges.value, rs,
-                 d_rsub.value, None)
             tmp = [DeviceBuffer(4 * n_res), DeviceBuffer(4 * n_res), DeviceBuffer(4 * n_res), DeviceBuffer(n_res),
                    DeviceBuffer(4 * n_res)]
-            call("fwav_affine", d_rsub.value, n_res, rs, d_newc.value, k, d_pool.value, nd, sc, *[b.value for b in tmp],
-                 None)
-            call("fwav_tie_rows_out", d_rows.value, n_res, *[b.value for b in tmp], *[b.value for b in outs], None)
+            stages.tie_fixup(d_rows.value, n_res, d_newc.value, k, d_cand.value, d_ranges.value, rs, d_rsub.value,
+                             [b.value for b in tmp], [b.value for b in outs], d_pool.value, nd, sc, None)
     kept, nd_out = None, nd
     if compact:
         # after the tie fix-ups (they change idx): only the rows that the matches name, indices renumbered in place
-        cap = min(nd, max(nr, 1))
+        cap = stages.compact_rows_cap(nd, nr)
         d_cpool, d_kept, d_counts = DeviceBuffer(4 * cap * rs), DeviceBuffer(4 * cap), DeviceBuffer(16)
         wsc = size_call("fwav_compact_workspace_size", nd, nr)
         d_wsc = DeviceBuffer(wsc)
         call("fwav_compact_domains", outs[0].value, nr, d_pool.value, nd, rs, outs[0].value, d_cpool.value,
              d_kept.value, d_counts.value, d_wsc.value, wsc, None)
         call("fwav_stream_sync", None)
-        nd_out, over = (int(v) for v in d_counts.to_array(np.int64, 2))
-        if over:
-            raise IndexError("domain index out of range")
+        nd_out = stages.compact_count(d_counts.to_array(np.int64, 2))
         kept = _i32(d_kept, nd_out)
         d_pool = d_cpool
     call("fwav_stream_sync", None)
@@ -330,29 +277,22 @@ def decompress(idx: np.ndarray, s: np.ndarray, o: np.ndarray, sym: np.ndarray, p
     d_state = DeviceBuffer.from_array(np.zeros(4, np.int32))
     wsn = size_call("fwav_decode_workspace_size", nr, rs, it)
     d_ws = DeviceBuffer(max(wsn, 16))
-    eps = float(convergence_eps)
-    done, d_init = 0, None
-    while True:
-        call("fwav_decode_from", *[b.value for b in d], nr, rs, d_pool.value, nd, it - done, eps,
-             float(abs(np.float32(s_clip))), float(s_damping), None if d_init is None else d_init.value, d_a.value,
-             d_b.value, d_del.value + 8 * done, d_state.value, d_ws.value, wsn, None)
+    d_init = []  # the reconstruction a resumed loop starts from, allocated at the first resume
+
+    def read_state():
         call("fwav_stream_sync", None)
-        state = _i32(d_state, 4)
-        ran = int(state[1])
-        res, other = (d_b, d_a) if int(state[2]) == 1 else (d_a, d_b)
-        if int(state[0]) == 2:  # the early-exit check in the reference's own sdot order (fractal.py:1460-1465)
-            call("fwav_decode_exact", other.value, res.value, nr * rs, eps, ran - 1, d_del.value + 8 * done,
-                 d_state.value, None)
-            call("fwav_stream_sync", None)
-            if int(_i32(d_state, 1)[0]) == 3 and done + ran < it:  # the reference goes on: resume from here
-                if d_init is None:
-                    d_init = DeviceBuffer(4 * max(nr * rs, 1))
-                _ck(hip().hipMemcpy(d_init.ptr, res.ptr, 4 * nr * rs, 3), "hipMemcpy")  # device to device
-                done += ran
-                continue
-        done += ran
-        break
-    ran = done
+        return _i32(d_state, 4)
+
+    def snapshot(ptr):
+        if not d_init:
+            d_init.append(DeviceBuffer(4 * max(nr * rs, 1)))
+        _ck(hip().hipMemcpy(d_init[0].ptr, ptr, 4 * nr * rs, 3), "hipMemcpy")  # device to device
+        return d_init[0].value
+
+    in_b, ran = stages.decode(*[b.value for b in d], nr, rs, d_pool.value, nd, it, float(convergence_eps),
+                              stages.clip32(s_clip), float(s_damping), d_a.value, d_b.value, d_del.value, d_state.value,
+                              d_ws.value, wsn, None, read_state=read_state, snapshot=snapshot)
+    res = d_b if in_b else d_a
     out = res.to_array(np.float32, nr * rs)
     if original_len is not None:
         out = out[:original_len]

@@ -25,7 +25,7 @@ import time
 import numpy as np
 import torch
 
-from ._lib import call
+from . import stages
 from .nporder import blas_threads, numpy_topk_row  # noqa: F401  (re-exported: the numpy-only half of this module)
 
 #: device bytes of exact score rows computed per fwav_score_rows launch (the launch reads the embedding table once)
@@ -133,9 +133,8 @@ def score_row_launches(rows: torch.Tensor, *, emb: torch.Tensor, n_domains: int,
     """Yield (first row + first_row, device f32[m·nd] scores, event) per fwav_score_rows launch of at most
     ``budget`` bytes, each launch queued on the current stream (``stream``) when the generator reaches it.  A
     consumer that must hold one launch at a time delegates with ``yield from`` (a loop variable of its own would keep
-    the previous launch alive while this generator allocates the next).  ``emb_dim``: the width of ``emb``'s rows (32:
-    fwav_score_rows_dim).  ``qemb``: the table the query rows are read from when it is not ``emb`` itself
-    (fwav_score_rows_q: compress_audio(query="range"))."""
+    the previous launch alive while this generator allocates the next).  ``emb_dim``: the width of ``emb``'s rows.
+    ``qemb``: the table the query rows are read from when it is not ``emb`` itself (compress_audio(query="range"))."""
     nd = int(n_domains)
     n = rows.numel()
     per = max(1, min(n, budget // (4 * nd)))
@@ -143,15 +142,8 @@ def score_row_launches(rows: torch.Tensor, *, emb: torch.Tensor, n_domains: int,
         rb = rows[b0:b0 + per].contiguous()
         m = rb.numel()
         S = torch.empty(m * nd, dtype=torch.float32, device=rows.device)
-        if qemb is not None:
-            call("fwav_score_rows_q", emb.data_ptr(), nd, qemb.data_ptr(), rb.data_ptr(), m, int(q_offset),
-                 int(threads), S.data_ptr(), stream)
-        elif emb_dim == 16:
-            call("fwav_score_rows", emb.data_ptr(), nd, rb.data_ptr(), m, int(q_offset), int(threads), S.data_ptr(),
-                 stream)
-        else:
-            call("fwav_score_rows_dim", emb.data_ptr(), nd, int(emb_dim), rb.data_ptr(), m, int(q_offset), int(threads),
-                 S.data_ptr(), stream)
+        stages.score_rows(emb.data_ptr(), nd, rb.data_ptr(), m, int(q_offset), int(threads), S.data_ptr(), stream,
+                          emb_dim=int(emb_dim), qemb=None if qemb is None else qemb.data_ptr())
         ev = torch.cuda.Event()
         ev.record()
         yield b0 + first_row, S, ev
@@ -280,13 +272,10 @@ def apply_rows(rows: torch.Tensor, futs: list, *, ranges: torch.Tensor, range_si
     rows = rows.contiguous()
     rs = int(range_size)
     rsub = torch.empty(n * rs, dtype=torch.float32, device=dev)
-    # three launches: candidate rows scattered + their ranges gathered, the affine re-solve, the outputs scattered
-    call("fwav_tie_rows_in", rows.data_ptr(), n, newc.data_ptr(), k, cand.data_ptr(), ranges.data_ptr(), rs,
-         rsub.data_ptr(), stream)
     tmp = [torch.empty(n, dtype=t.dtype, device=dev) for t in outs]
-    call("fwav_affine", rsub.data_ptr(), n, rs, newc.data_ptr(), k, pool.data_ptr(), int(n_domains), float(s_clip),
-         *[t.data_ptr() for t in tmp], stream)
-    call("fwav_tie_rows_out", rows.data_ptr(), n, *[t.data_ptr() for t in tmp], *[t.data_ptr() for t in outs], stream)
+    stages.tie_fixup(rows.data_ptr(), n, newc.data_ptr(), k, cand.data_ptr(), ranges.data_ptr(), rs, rsub.data_ptr(),
+                     [t.data_ptr() for t in tmp], [t.data_ptr() for t in outs], pool.data_ptr(), int(n_domains),
+                     float(s_clip), stream)
 
 
 def resolve_rows(rows: torch.Tensor, *, emb: torch.Tensor, n_domains: int, q_offset: int, k: int, threads: int,

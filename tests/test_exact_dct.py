@@ -117,13 +117,13 @@ def test_python_layers_take_the_mode_and_refuse_bad_ones(L):
     a range size without a plan, are ValueErrors that name the range size (checked before any device work)."""
     import inspect
 
-    from fwav import api, cli, dist, engine, hipctypes
+    from fwav import api, cli, dist, engine, hipctypes, stages
     for fn in (engine._compress_device, api.compress_audio, api.process_file_compress, hipctypes.compress,
                hipctypes.pool_embed, dist.compress_sharded, dist.compress_sharded_device, dist.compress_sharded_start):
         assert inspect.signature(fn).parameters["embedding"].default == "matrix", fn
     assert engine.check_embedding("pocketfft", 32) == "pocketfft"
     assert engine.check_embedding("matrix", 51) == "matrix"
-    for check in (engine.check_embedding, lambda m, rs: hipctypes._embed_tables(rs, m)):
+    for check in (engine.check_embedding, lambda m, rs: stages.embed_tables_host(rs, m)):
         with pytest.raises(ValueError, match="range size 51"):
             check("pocketfft", 51)
         with pytest.raises(ValueError, match="'matrix' or 'pocketfft'"):
