@@ -95,18 +95,22 @@ __device__ __forceinline__ auto pw_rec(const F& f, int off, int n) -> decltype(f
 
 // np.add.reduce over n <= kMaxPairwise elements: numpy starts the output at 0 (so -0 sums to +0).
 constexpr int kMaxPairwise = 1024;
+// Levels of splitting pw_sum needs before every part is a leaf of at most 128 elements.  The right part of a split
+// has up to n/2 + 7 elements, so three levels are not enough for 49 of the lengths from 969 to 1023: 1023 → 519 → 263
+// → 135, which numpy splits once more (64 + 71).  Four levels reach a leaf for every n ≤ kMaxPairwise.
+constexpr int kPairwiseDepth = 4;
 // Records of the search's tie list (fwav_sim_topk `ties`): the query, then its K-th place tie group (fwav_topk.hip
 // record_tie), int32 each.
 constexpr int kTieRec = 9;
 template <class F>
 __device__ __forceinline__ auto pw_sum(const F& f, int n) -> decltype(f(0)) {
-  return 0.0f + pw_rec<3>(f, 0, n);
+  return 0.0f + pw_rec<kPairwiseDepth>(f, 0, n);
 }
 
 // Compile-time-length variant (fully unrolled, register-resident operands).
 template <int N, class F>
 __device__ __forceinline__ auto pw_sum_n(const F& f) -> decltype(f(0)) {
-  return 0.0f + pw_rec<3>(f, 0, N);
+  return 0.0f + pw_rec<kPairwiseDepth>(f, 0, N);
 }
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
