@@ -487,11 +487,11 @@ def topk_candidates_loop(emb: np.ndarray, rows: np.ndarray, k: int) -> np.ndarra
 
 
 # ----------------------------------------------------------------------------------- affine (a5)
-def affine(ranges: np.ndarray, cand: np.ndarray, pool: np.ndarray, s_clip: float = 16.0):
-    """_process_gpu_batch (fractal.py:757-850), float32 in numpy order.  Returns SoA (idx, s, o, sym, err)."""
+def affine_slots(ranges: np.ndarray, cand: np.ndarray, pool: np.ndarray):
+    """The per-slot half of _process_gpu_batch (fractal.py:757-815): for every range the unclipped s, o and the error
+    of each of its 2K slots [K candidates | K mirrored] (+inf where cand < 0), float32 in numpy order.  Returns
+    (s, o, err), each (B, 2K).  A slot's values depend on its range and its tile alone."""
     ranges = np.asarray(ranges, F32)
-    B, N = ranges.shape
-    K = cand.shape[1]
     safe = np.where(cand < 0, 0, cand)
     dom = pool[safe]                                     # (B, K, N)
     dsym = np.concatenate([dom, dom[:, :, ::-1]], axis=1)  # (B, 2K, N) contiguous
@@ -507,7 +507,15 @@ def affine(ranges: np.ndarray, cand: np.ndarray, pool: np.ndarray, s_clip: float
     diff = recon - ranges[:, None, :]
     err = np.sqrt(pw_sum(diff * diff))
     inval = np.concatenate([cand < 0, cand < 0], axis=1)
-    err = np.where(inval, F32(np.inf), err)
+    return s, o, np.where(inval, F32(np.inf), err)
+
+
+def affine(ranges: np.ndarray, cand: np.ndarray, pool: np.ndarray, s_clip: float = 16.0):
+    """_process_gpu_batch (fractal.py:757-850), float32 in numpy order.  Returns SoA (idx, s, o, sym, err)."""
+    B = len(ranges)
+    K = cand.shape[1]
+    safe = np.where(cand < 0, 0, cand)
+    s, o, err = affine_slots(ranges, cand, pool)
     j = np.argmin(err, axis=1)
     ar = np.arange(B)
     c = abs(F32(s_clip))
