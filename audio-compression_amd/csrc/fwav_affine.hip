@@ -14,6 +14,14 @@
 // reference (tests/test_gpu_parity.py).  The argmin is a 6-step xor-shuffle reduction with numpy's
 // tie/NaN rules (first NaN wins, else smallest err, else lowest slot).
 // Bytes per range: 4·rs (range) + 4·K (candidates) + 4·K·rs (gathered rows) + 17 (outputs).
+//
+// Fit modes (template parameter FIT of the three solvers; fwav_affine_fit).  kFitReference is the above.  kFitClipped
+// (no counterpart in the reference; opt-in) selects by the error of the tuple that is stored: per slot
+//       s = clip(Σd̃r̃ / (Σd̃d̃ + 1e-12), ±|s_clip|)  (np.clip: NaN stays NaN);  o = r̄ − s·d̄;  err = ‖(s·D + o) − R‖₂
+// — the constrained least-squares scale for |s| ≤ |s_clip| — and the winner is the first NaN error, else the smallest
+// error, then the smaller clamped domain index, then unmirrored before mirrored: a function of the candidate set, not
+// of the candidates' order.  Slots that tie in all three hold the same tile in the same orientation, so the same
+// tuple.  The reference instantiations compile to the code they were before the parameter existed.
 #include "fwav_common.h"
 #include "../../include/fwav.h"
 
@@ -25,6 +33,7 @@
 namespace fwav {
 
 constexpr int kAffWaves = 4;
+constexpr int kFitReference = 0, kFitClipped = 1;
 
 struct Best {
   float err, s, o;
@@ -37,9 +46,24 @@ __device__ __forceinline__ bool better(float e1, int s1, float e2, int s2) {
   return e1 < e2 || (e1 == e2 && s1 < s2);
 }
 
-template <int RS>
+// better() with the tie-break keys compared as u32: kFitClipped's key is domain·2 + mirrored (kFitReference's: the slot)
+__device__ __forceinline__ bool better_key(float e1, int k1, float e2, int k2) {
+  const uint32_t u1 = (uint32_t)k1, u2 = (uint32_t)k2;
+  const bool n1 = e1 != e1, n2 = e2 != e2;
+  if (n1 || n2) return (n1 && n2) ? u1 < u2 : n1;
+  return e1 < e2 || (e1 == e2 && u1 < u2);
+}
+// (macros, not wrappers: the reference instantiations then hold the very calls they held before)
+#define FWAV_BETTER(e1, k1, e2, k2) (FIT == kFitClipped ? better_key(e1, k1, e2, k2) : better(e1, k1, e2, k2))
+#define FWAV_FIT_KEY(slot, di, mirrored) \
+  (FIT == kFitClipped ? (int)((uint32_t)(di) * 2u + (uint32_t)(mirrored)) : (slot))
+// the key no slot has: it loses every tie
+template <int FIT>
+constexpr int kNoSlot = FIT == kFitClipped ? -1 : 0x7fffffff;
+
+template <int RS, int FIT = kFitReference>
 __device__ __forceinline__ void eval_orient(const float (&X)[RS], const float (&R)[RS], const float (&rc)[RS], float rm,
-                                            float& s, float& o, float& err) {
+                                            float& s, float& o, float& err, float c = 0.f) {
   auto fx = [&](int i) { return X[i]; };
   const float dm = pw_sum_n<RS>(fx) / (float)RS;
   float dc[RS];
@@ -50,6 +74,7 @@ __device__ __forceinline__ void eval_orient(const float (&X)[RS], const float (&
   const float num = pw_sum_n<RS>(fn);
   const float den = pw_sum_n<RS>(fd) + 1e-12f;
   s = num / den;
+  if constexpr (FIT == kFitClipped) s = clip_sym(s, c);
   o = rm - s * dm;
   auto fe = [&](int i) {
     const float df = (s * X[i] + o) - R[i];
@@ -58,7 +83,7 @@ __device__ __forceinline__ void eval_orient(const float (&X)[RS], const float (&
   err = sqrtf(pw_sum_n<RS>(fe));
 }
 
-template <int RS>
+template <int RS, int FIT>
 __global__ __launch_bounds__(64 * kAffWaves) void k_affine(const float* __restrict__ ranges, int64_t nr,
                                                            const int32_t* __restrict__ cand, int K,
                                                            const float* __restrict__ pool, float s_clip,
@@ -76,7 +101,8 @@ __global__ __launch_bounds__(64 * kAffWaves) void k_affine(const float* __restri
 #pragma unroll
   for (int i = 0; i < RS; ++i) rc[i] = R[i] - rm;
 
-  Best b{INFINITY, 0.f, 0.f, 0x7fffffff, 0};
+  const float sc = fabsf(s_clip);
+  Best b{INFINITY, 0.f, 0.f, kNoSlot<FIT>, 0};
   bool have = false;
   const int32_t* cr = cand + r * (int64_t)K;
   for (int c = lane; c < K; c += 64) {
@@ -97,11 +123,15 @@ __global__ __launch_bounds__(64 * kAffWaves) void k_affine(const float* __restri
 #pragma unroll
     for (int i = 0; i < RS; ++i) M[i] = D[RS - 1 - i];
     float s0, o0, e0, s1, o1, e1;
-    eval_orient<RS>(D, R, rc, rm, s0, o0, e0);
-    eval_orient<RS>(M, R, rc, rm, s1, o1, e1);
+    eval_orient<RS, FIT>(D, R, rc, rm, s0, o0, e0, sc);
+    eval_orient<RS, FIT>(M, R, rc, rm, s1, o1, e1, sc);
     if (ci < 0) { e0 = INFINITY; e1 = INFINITY; }
-    if (!have || better(e0, c, b.err, b.slot)) { b = Best{e0, s0, o0, c, di}; have = true; }
-    if (better(e1, K + c, b.err, b.slot)) b = Best{e1, s1, o1, K + c, di};
+    if (!have || FWAV_BETTER(e0, FWAV_FIT_KEY(c, di, 0), b.err, b.slot)) {
+      b = Best{e0, s0, o0, FWAV_FIT_KEY(c, di, 0), di};
+      have = true;
+    }
+    if (FWAV_BETTER(e1, FWAV_FIT_KEY(K + c, di, 1), b.err, b.slot))
+      b = Best{e1, s1, o1, FWAV_FIT_KEY(K + c, di, 1), di};
   }
 #pragma unroll
   for (int m = 1; m < 64; m <<= 1) {
@@ -111,18 +141,19 @@ __global__ __launch_bounds__(64 * kAffWaves) void k_affine(const float* __restri
     o.o = __shfl_xor(b.o, m);
     o.slot = __shfl_xor(b.slot, m);
     o.dom = __shfl_xor(b.dom, m);
-    if (better(o.err, o.slot, b.err, b.slot)) b = o;
+    if (FWAV_BETTER(o.err, o.slot, b.err, b.slot)) b = o;
   }
   if (lane == 0) {
     out_idx[r] = b.dom;
-    out_s[r] = clip_sym(b.s, fabsf(s_clip));
+    out_s[r] = clip_sym(b.s, sc);  // (kFitClipped: already clipped; the clip is idempotent)
     out_o[r] = b.o;
-    out_sym[r] = (uint8_t)(b.slot >= K);
+    out_sym[r] = (uint8_t)(FIT == kFitClipped ? (b.slot & 1) : (b.slot >= K));
     out_err[r] = b.err;
   }
 }
 
 // Generic rs (runtime), rows read from global memory; same arithmetic.
+template <int FIT>
 __global__ __launch_bounds__(64 * kAffWaves) void k_affine_any(const float* __restrict__ ranges, int64_t nr, int rs,
                                                                const int32_t* __restrict__ cand, int K,
                                                                const float* __restrict__ pool, float s_clip,
@@ -135,7 +166,7 @@ __global__ __launch_bounds__(64 * kAffWaves) void k_affine_any(const float* __re
   const float* R = ranges + r * rs;
   auto fr = [&](int i) { return R[i]; };
   const float rm = pw_sum(fr, rs) / (float)rs;
-  Best b{INFINITY, 0.f, 0.f, 0x7fffffff, 0};
+  Best b{INFINITY, 0.f, 0.f, kNoSlot<FIT>, 0};
   bool have = false;
   const int32_t* cr = cand + r * (int64_t)K;
   for (int c = lane; c < K; c += 64) {
@@ -152,7 +183,7 @@ __global__ __launch_bounds__(64 * kAffWaves) void k_affine_any(const float* __re
       };
       const float num = pw_sum(fn, rs);
       const float den = pw_sum(fd, rs) + 1e-12f;
-      const float s = num / den;
+      const float s = FIT == kFitClipped ? clip_sym(num / den, fabsf(s_clip)) : num / den;
       const float o = rm - s * dm;
       auto fe = [&](int i) {
         const float df = (s * X(i) + o) - R[i];
@@ -160,8 +191,8 @@ __global__ __launch_bounds__(64 * kAffWaves) void k_affine_any(const float* __re
       };
       float e = sqrtf(pw_sum(fe, rs));
       if (ci < 0) e = INFINITY;
-      const int slot = orient * K + c;
-      if (!have || better(e, slot, b.err, b.slot)) { b = Best{e, s, o, slot, di}; have = true; }
+      const int slot = FWAV_FIT_KEY(orient * K + c, di, orient);
+      if (!have || FWAV_BETTER(e, slot, b.err, b.slot)) { b = Best{e, s, o, slot, di}; have = true; }
     }
   }
 #pragma unroll
@@ -172,17 +203,20 @@ __global__ __launch_bounds__(64 * kAffWaves) void k_affine_any(const float* __re
     o.o = __shfl_xor(b.o, m);
     o.slot = __shfl_xor(b.slot, m);
     o.dom = __shfl_xor(b.dom, m);
-    if (better(o.err, o.slot, b.err, b.slot)) b = o;
+    if (FWAV_BETTER(o.err, o.slot, b.err, b.slot)) b = o;
   }
   if (lane == 0) {
     out_idx[r] = b.dom;
     out_s[r] = clip_sym(b.s, fabsf(s_clip));
     out_o[r] = b.o;
-    out_sym[r] = (uint8_t)(b.slot >= K);
+    out_sym[r] = (uint8_t)(FIT == kFitClipped ? (b.slot & 1) : (b.slot >= K));
     out_err[r] = b.err;
   }
 }
 
+
+#undef FWAV_BETTER
+#undef FWAV_FIT_KEY
 
 // ------------------------------------------------------------------ batched kernel (K <= 64, rs 4/8/16)
 // Lane c ↔ candidate c; a wave handles kAffBatch consecutive ranges.  Per range the work is two dependent
@@ -193,7 +227,8 @@ __global__ __launch_bounds__(64 * kAffWaves) void k_affine_any(const float* __re
 // are evaluated together in packed f32 (v_pk_mul_f32 / v_pk_add_f32; each half is one correctly rounded f32
 // op, so the numpy order and results are unchanged) — the VALU is the bound here, at 4 cycles per wave64
 // op.  The argmin is two DPP wave reductions on (NaN-first error order, slot) followed by readlanes of the
-// winner, instead of a 5-value shuffle tree.
+// winner, instead of a 5-value shuffle tree.  kFitClipped: the second reduction is over domain·2 + mirrored, which
+// several lanes can hold (one domain twice in a row), so the winning lane is the first of a ballot.
 template <int RS>
 __device__ __forceinline__ void gather_row(const float* __restrict__ pool, int32_t ci, float (&D)[RS]) {
   const int64_t di = ci < 0 ? 0 : ci;
@@ -212,7 +247,7 @@ __device__ __forceinline__ void gather_row(const float* __restrict__ pool, int32
 
 extern "C" __device__ uint32_t __ockl_wfred_min_u32(uint32_t);
 
-template <int RS>
+template <int RS, int FIT>
 __device__ __forceinline__ void affine_one(const float (&R)[RS], int64_t r, int32_t ci, bool has,
                                            int K, const float (&D)[RS], float s_clip, int32_t* out_idx,
                                            float* out_s, float* out_o, uint8_t* out_sym, float* out_err) {
@@ -236,7 +271,8 @@ __device__ __forceinline__ void affine_one(const float (&R)[RS], int64_t r, int3
   const f32x2 den = pw_sum_n<RS>(fd) + 1e-12f;
   auto fn = [&](int i) { return dc[i] * rc[i]; };
   const f32x2 num = pw_sum_n<RS>(fn);
-  const f32x2 sv = num / den;
+  f32x2 sv = num / den;
+  if constexpr (FIT == kFitClipped) sv = f32x2{clip_sym(sv.x, fabsf(s_clip)), clip_sym(sv.y, fabsf(s_clip))};
   const f32x2 ov = rm - sv * dm;
   auto fe = [&](int i) {
     const f32x2 df = (sv * X[i] + ov) - R[i];
@@ -251,6 +287,24 @@ __device__ __forceinline__ void affine_one(const float (&R)[RS], int64_t r, int3
   const uint32_t slot = take1 ? (uint32_t)(K + lane) : (uint32_t)lane;
   const uint32_t ekey = has ? ((eb != eb) ? 0u : __float_as_uint(eb) + 1u) : 0xffffffffu;
   const uint32_t kmin = __ockl_wfred_min_u32(ekey);
+  if constexpr (FIT == kFitClipped) {
+    // (err key, domain·2 + mirrored): the lane's two slots hold one domain, so its own best is the one above
+    const uint32_t dkey = (uint32_t)(ci < 0 ? 0 : ci) * 2u + (take1 ? 1u : 0u);
+    const uint32_t dmin = __ockl_wfred_min_u32((has && ekey == kmin) ? dkey : 0xffffffffu);
+    const int wl = __builtin_ctzll(__ballot(has && ekey == kmin && dkey == dmin));  // lane 0 has a slot: never empty
+    auto bcast = [&](float v) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), wl)); };
+    const float sb = bcast(take1 ? sv.y : sv.x);
+    const float ob = bcast(take1 ? ov.y : ov.x);
+    const float erb = bcast(eb);
+    if (lane == 0) {
+      out_idx[r] = (int32_t)(dmin >> 1);
+      out_s[r] = sb;
+      out_o[r] = ob;
+      out_sym[r] = (uint8_t)(dmin & 1u);
+      out_err[r] = erb;
+    }
+    return;
+  }
   const uint32_t smin = __ockl_wfred_min_u32((has && ekey == kmin) ? slot : 0xffffffffu);
   const int wl = (int)(smin < (uint32_t)K ? smin : smin - (uint32_t)K);
   auto bcast = [&](float v) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), wl)); };
@@ -278,7 +332,7 @@ constexpr int kAffBatch = FWAV_AFF_BATCH;  // ranges per wave in k_affine_batch
 #define FWAV_AFF_XCD 1
 #endif
 
-template <int RS>
+template <int RS, int FIT>
 __global__ __launch_bounds__(64 * kAffWaves) void k_affine_batch(const float* __restrict__ ranges, int64_t nr,
                                                                  const int32_t* __restrict__ cand, int K,
                                                                  const float* __restrict__ pool, float s_clip,
@@ -328,7 +382,7 @@ __global__ __launch_bounds__(64 * kAffWaves) void k_affine_batch(const float* __
     float R[RS];
 #pragma unroll
     for (int i = 0; i < RS; ++i) R[i] = rg[r * RS + i];
-    affine_one<RS>(R, r, has ? c[j] : -1, has, K, D[j], s_clip, out_idx, out_s, out_o, out_sym, out_err);
+    affine_one<RS, FIT>(R, r, has ? c[j] : -1, has, K, D[j], s_clip, out_idx, out_s, out_o, out_sym, out_err);
   }
 }
 
@@ -542,6 +596,45 @@ __global__ __launch_bounds__(256) void k_tie_rows_out(const int32_t* __restrict_
 
 using namespace fwav;
 
+template <int FIT>
+static int affine_launch(const char* what, const float* ranges, int64_t nr, int rs, const int32_t* cand, int K,
+                         const float* pool, int64_t nd, float s_clip, int32_t* out_idx, float* out_s, float* out_o,
+                         uint8_t* out_sym, float* out_err, void* stream) {
+  FWAV_CHECK_ARG(ranges && cand && pool && out_idx && out_s && out_o && out_sym && out_err, FWAV_ERR_ARG,
+                 "%s: null pointer", what);
+  FWAV_CHECK_ARG(nr >= 0 && rs >= 1 && K >= 1 && nd >= 1, FWAV_ERR_SHAPE, "%s: bad shape", what);
+  FWAV_CHECK_ARG(rs <= kMaxPairwise, FWAV_ERR_SHAPE, "%s: rs > %d", what, kMaxPairwise);
+  if (nr == 0) return FWAV_OK;
+  hipStream_t st = (hipStream_t)stream;
+  const int64_t grid = cdiv(nr, kAffWaves);
+  const int thr = 64 * kAffWaves;
+  if (K <= 64 && (rs == 4 || rs == 8 || rs == 16)) {
+    switch (rs) {
+#define FWAV_AFF_PIPE(RSV)                                                                                        \
+  case RSV:                                                                                                       \
+    k_affine_batch<RSV, FIT><<<cdiv(nr, kAffWaves * kAffBatch), thr, 0, st>>>(ranges, nr, cand, K, pool, s_clip,  \
+                                                                              out_idx, out_s, out_o, out_sym,     \
+                                                                              out_err);                           \
+    break;
+      FWAV_AFF_PIPE(4)
+      FWAV_AFF_PIPE(8)
+      FWAV_AFF_PIPE(16)
+#undef FWAV_AFF_PIPE
+    }
+    FWAV_LAUNCH_CHECK(what);
+    return FWAV_OK;
+  }
+  switch (rs) {
+    case 4: k_affine<4, FIT><<<grid, thr, 0, st>>>(ranges, nr, cand, K, pool, s_clip, out_idx, out_s, out_o, out_sym, out_err); break;
+    case 8: k_affine<8, FIT><<<grid, thr, 0, st>>>(ranges, nr, cand, K, pool, s_clip, out_idx, out_s, out_o, out_sym, out_err); break;
+    case 16: k_affine<16, FIT><<<grid, thr, 0, st>>>(ranges, nr, cand, K, pool, s_clip, out_idx, out_s, out_o, out_sym, out_err); break;
+    default:
+      k_affine_any<FIT><<<grid, thr, 0, st>>>(ranges, nr, rs, cand, K, pool, s_clip, out_idx, out_s, out_o, out_sym, out_err);
+  }
+  FWAV_LAUNCH_CHECK(what);
+  return FWAV_OK;
+}
+
 extern "C" {
 
 int fwav_debug_gather_rows(const float* table, int64_t n_rows, int rs, int64_t n, float* sink, void* stream) {
@@ -617,38 +710,19 @@ int fwav_tie_check_dim(const float* ranges, int64_t n_ranges, int rs, const int3
 int fwav_affine(const float* ranges, int64_t nr, int rs, const int32_t* cand, int K, const float* pool, int64_t nd,
                 float s_clip, int32_t* out_idx, float* out_s, float* out_o, uint8_t* out_sym, float* out_err,
                 void* stream) {
-  FWAV_CHECK_ARG(ranges && cand && pool && out_idx && out_s && out_o && out_sym && out_err, FWAV_ERR_ARG,
-                 "fwav_affine: null pointer");
-  FWAV_CHECK_ARG(nr >= 0 && rs >= 1 && K >= 1 && nd >= 1, FWAV_ERR_SHAPE, "fwav_affine: bad shape");
-  FWAV_CHECK_ARG(rs <= kMaxPairwise, FWAV_ERR_SHAPE, "fwav_affine: rs > %d", kMaxPairwise);
-  if (nr == 0) return FWAV_OK;
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t grid = cdiv(nr, kAffWaves);
-  const int thr = 64 * kAffWaves;
-  if (K <= 64 && (rs == 4 || rs == 8 || rs == 16)) {
-    switch (rs) {
-#define FWAV_AFF_PIPE(RSV)                                                                                   \
-  case RSV:                                                                                                  \
-    k_affine_batch<RSV><<<cdiv(nr, kAffWaves * kAffBatch), thr, 0, st>>>(ranges, nr, cand, K, pool, s_clip,  \
-                                                                         out_idx, out_s, out_o, out_sym, out_err); \
-    break;
-      FWAV_AFF_PIPE(4)
-      FWAV_AFF_PIPE(8)
-      FWAV_AFF_PIPE(16)
-#undef FWAV_AFF_PIPE
-    }
-    FWAV_LAUNCH_CHECK("fwav_affine");
-    return FWAV_OK;
-  }
-  switch (rs) {
-    case 4: k_affine<4><<<grid, thr, 0, st>>>(ranges, nr, cand, K, pool, s_clip, out_idx, out_s, out_o, out_sym, out_err); break;
-    case 8: k_affine<8><<<grid, thr, 0, st>>>(ranges, nr, cand, K, pool, s_clip, out_idx, out_s, out_o, out_sym, out_err); break;
-    case 16: k_affine<16><<<grid, thr, 0, st>>>(ranges, nr, cand, K, pool, s_clip, out_idx, out_s, out_o, out_sym, out_err); break;
-    default:
-      k_affine_any<<<grid, thr, 0, st>>>(ranges, nr, rs, cand, K, pool, s_clip, out_idx, out_s, out_o, out_sym, out_err);
-  }
-  FWAV_LAUNCH_CHECK("fwav_affine");
-  return FWAV_OK;
+  return affine_launch<kFitReference>("fwav_affine", ranges, nr, rs, cand, K, pool, nd, s_clip, out_idx, out_s, out_o,
+                                      out_sym, out_err, stream);
+}
+
+int fwav_affine_fit(const float* ranges, int64_t nr, int rs, const int32_t* cand, int K, const float* pool, int64_t nd,
+                    float s_clip, int32_t* out_idx, float* out_s, float* out_o, uint8_t* out_sym, float* out_err,
+                    int fit, void* stream) {
+  FWAV_CHECK_ARG(fit == kFitReference || fit == kFitClipped, FWAV_ERR_ARG,
+                 "fwav_affine_fit: fit %d (0: reference, 1: clipped)", fit);
+  if (fit == kFitReference)
+    return fwav_affine(ranges, nr, rs, cand, K, pool, nd, s_clip, out_idx, out_s, out_o, out_sym, out_err, stream);
+  return affine_launch<kFitClipped>("fwav_affine_fit", ranges, nr, rs, cand, K, pool, nd, s_clip, out_idx, out_s,
+                                    out_o, out_sym, out_err, stream);
 }
 
 int fwav_tie_rows_in(const int32_t* rows, int64_t n, const int32_t* new_cand, int K, int32_t* cand,

@@ -51,6 +51,7 @@ SIGNATURES = {
     "fwav_score_rows": (I32, [P, I64, P, I64, I64, I32, P, P]),
     "fwav_debug_gather_rows": (I32, [P, I64, I32, I64, P, P]),
     "fwav_affine": (I32, [P, I64, I32, P, I32, P, I64, F32, P, P, P, P, P, P]),
+    "fwav_affine_fit": (I32, [P, I64, I32, P, I32, P, I64, F32, P, P, P, P, P, I32, P]),
     "fwav_tie_check": (I32, [P, I64, I32, P, I32, P, I64, P, I64, I32, P, I64, I32, P, P]),
     "fwav_tie_rows_in": (I32, [P, I64, P, I32, P, P, I32, P, P]),
     "fwav_tie_rows_out": (I32, [P, I64, P, P, P, P, P, P, P, P, P, P, P]),

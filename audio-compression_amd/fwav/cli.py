@@ -2,12 +2,14 @@
 
   python fractal.py compress IN OUT [--tile 1024] [--energy-thresh 1e-4] [--gpu] [--batch] [--out DIR] [--workers 4]
                             [--embedding {matrix,pocketfft}] [--emb-dim {16,32}]
-                            [--compact] [--query {domain_row,range}]
+                            [--compact] [--query {domain_row,range}] [--fit {reference,clipped}]
   python fractal.py decompress IN [--out PATH] [--iter 8] [--eps 1e-3] [--gpu] [--batch] [--workers 4]
                               [--s-damping 0.0]
   python fractal.py compact IN.fwav [--out PATH]
 
---embedding, --emb-dim, --compact, --query, --s-damping and the compact sub-command are this port's extras.  --query
+--embedding, --emb-dim, --compact, --query, --fit, --s-damping and the compact sub-command are this port's extras.  --fit
+clipped stores, among the same candidates, the match whose stored tuple (s clipped to ±16 first) fits best, and the
+error of that tuple; the default is the reference's selection by the unclipped scale.  --query
 range searches with each range's own embedding instead of the reference pipeline's domain row i (quirk Q1): better
 matches, not the reference's file; they reach the decoded signal through --s-damping d with a small positive d
 (decompress_audio's s_damping, fractal.py:1445; at the reference's 0.0 the decoder uses s = 0).  --compact stores only the
@@ -102,6 +104,9 @@ def build_parser() -> argparse.ArgumentParser:
     pc.add_argument("--query", choices=("domain_row", "range"), default="domain_row",
                     help="range i's query vector: domain-embedding row i (the reference's pipeline) or the embedding "
                          "of the range itself (closer matches; not the reference's file)")
+    pc.add_argument("--fit", choices=("reference", "clipped"), default="reference",
+                    help="match selection: by the error of the unclipped scale, as the reference (s is clipped "
+                         "afterwards), or by the error of the tuple that is stored (not the reference's file)")
     pk = sub.add_parser("compact")
     pk.add_argument("input", help="input FWAV file")
     pk.add_argument("--out", default=None, help="output FWAV file (default: IN with .compact.fwav for .fwav)")
@@ -129,7 +134,7 @@ def main(argv=None):
             if args.output is None:
                 parser.error("compress requires OUTPUT unless --batch is used")
             return _compress_job((args.input, args.output, args.tile, args.energy_thresh, args.gpu, args.embedding,
-                                  args.emb_dim, args.compact, args.query))
+                                  args.emb_dim, args.compact, args.query, args.fit))
         if args.output is not None:
             parser.error("Do not provide positional OUTPUT when using --batch; use --out instead")
         out_dir = args.out or args.input
@@ -141,7 +146,7 @@ def main(argv=None):
             return None
         results = _run_pool(_compress_job, [(f, os.path.join(out_dir, os.path.basename(f) + ".fwav"), args.tile,
                                              args.energy_thresh, args.gpu, args.embedding, args.emb_dim, args.compact,
-                                             args.query)
+                                             args.query, args.fit)
                                             for f in todo],
                             args.workers)
         metrics_file = os.path.join(out_dir, "compression_metrics.json")

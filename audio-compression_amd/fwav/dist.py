@@ -132,10 +132,10 @@ def _unpack(packed: torch.Tensor, blocks) -> dict:
 
 
 # ------------------------------------------------------------------------------------------------ compress
-def _device_compute(sig, tile_size, top_k, energy_thresh, shard, embedding="matrix", emb_dim=16):
+def _device_compute(sig, tile_size, top_k, energy_thresh, shard, embedding="matrix", emb_dim=16, fit="reference"):
     from .engine import compress_device
     r = compress_device(sig, tile_size, top_k, energy_thresh=energy_thresh, shard=shard, embedding=embedding,
-                        emb_dim=emb_dim)
+                        emb_dim=emb_dim, fit=fit)
     if r.empty:
         return None
     return dict(idx=r.idx, s=r.s, o=r.o, sym=r.sym, err=r.err, pool=r.pool, n_ranges=r.n_ranges,
@@ -145,23 +145,24 @@ def _device_compute(sig, tile_size, top_k, energy_thresh, shard, embedding="matr
 def compress_sharded_device(sig: Optional[torch.Tensor], tile_size: int, top_k: int, energy_thresh: float = 1e-4,
                             group=None, device: Optional[torch.device] = None, compute: Optional[Callable] = None,
                             timings: Optional[dict] = None, n: Optional[int] = None, embedding: str = "matrix",
-                            emb_dim: int = 16):
+                            emb_dim: int = 16, fit: str = "reference"):
     """The sharded compress on device tensors.  ``sig`` (1-D f32, on ``device``) is needed on rank 0 only.
     Returns on rank 0 a dict of full-length device tensors idx/s/o/sym/err, the pool, the blocks and geometry, and
     ``is_silent()`` (the reference's silent-input test, one device read); None on the other ranks (``empty=True``
     without arrays for empty / short input).  ``n`` (the signal length, if every rank knows it) saves broadcasting it.
     ``timings`` (if given) receives per-phase host seconds (broadcast / compute / gather), each phase then closed by
     a device synchronisation (without it the phases run back to back, with no synchronisation of their own).
-    ``embedding`` and ``emb_dim`` as :func:`compress_sharded_start`.
+    ``embedding``, ``emb_dim`` and ``fit`` as :func:`compress_sharded_start`.
     Equal to ``compress_sharded_finish(compress_sharded_start(...))``."""
     return compress_sharded_finish(compress_sharded_start(sig, tile_size, top_k, energy_thresh, group, device, compute,
-                                                          timings, n, embedding=embedding, emb_dim=emb_dim))
+                                                          timings, n, embedding=embedding, emb_dim=emb_dim, fit=fit))
 
 
 def compress_sharded_start(sig: Optional[torch.Tensor], tile_size: int, top_k: int, energy_thresh: float = 1e-4,
                            group=None, device: Optional[torch.device] = None, compute: Optional[Callable] = None,
                            timings: Optional[dict] = None, n: Optional[int] = None,
-                           signal_ready: bool = False, embedding: str = "matrix", emb_dim: int = 16) -> dict:
+                           signal_ready: bool = False, embedding: str = "matrix", emb_dim: int = 16,
+                           fit: str = "reference") -> dict:
     """First half of :func:`compress_sharded_device`: the signal broadcast and this rank's search + solve, queued.
     ``compute`` may return a ``wait`` callable (a deferred tie resolution, engine.compress_device(defer_ties=True));
     :func:`compress_sharded_finish` calls it before the gather.  A stream of calls can keep a few started calls in
@@ -173,17 +174,20 @@ def compress_sharded_start(sig: Optional[torch.Tensor], tile_size: int, top_k: i
     every rank embeds the whole signal itself, so every rank must pass the same mode (as it must the same tile size).
     It is validated on every rank before the first collective; a ``compute`` of the caller's own chooses its embedding
     itself, so anything but "matrix" beside one is a ValueError.  ``emb_dim`` (16 or 32, as engine.compress_device)
-    likewise: the default compute's embedding width, the same on every rank, 16 beside a compute of the caller's."""
+    likewise: the default compute's embedding width, the same on every rank, 16 beside a compute of the caller's.
+    ``fit`` ("reference" or "clipped", as engine.compress_device) too: every rank solves its shard in that mode, so
+    every rank passes the same one; "reference" beside a compute of the caller's."""
     stages.check_embedding(embedding, geometry(tile_size)[0])
     stages.check_emb_dim(emb_dim, embedding)
-    if compute is not None and (embedding != "matrix" or emb_dim != 16):
-        raise ValueError("embedding and emb_dim apply to the default compute; a compute of your own passes them to "
-                         "compress_device itself")
+    stages.check_fit(fit)
+    if compute is not None and (embedding != "matrix" or emb_dim != 16 or fit != "reference"):
+        raise ValueError("embedding, emb_dim and fit apply to the default compute; a compute of your own passes them "
+                         "to compress_device itself")
     rank = dist.get_rank(group)
     world = dist.get_world_size(group)
     if device is None:
         device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
-    compute = compute or functools.partial(_device_compute, embedding=embedding, emb_dim=emb_dim)
+    compute = compute or functools.partial(_device_compute, embedding=embedding, emb_dim=emb_dim, fit=fit)
     tm = timings if timings is not None else {}
     timed = timings is not None
 
@@ -270,13 +274,13 @@ def compress_sharded_finish(h: dict):
 
 def compress_sharded(signal: Optional[np.ndarray], tile_size: int, top_k: int, energy_thresh: float = 1e-4,
                      group=None, device: Optional[torch.device] = None, compute: Optional[Callable] = None,
-                     embedding: str = "matrix", emb_dim: int = 16, compact: bool = False):
+                     embedding: str = "matrix", emb_dim: int = 16, compact: bool = False, fit: str = "reference"):
     """Compress one signal with its ranges split across the ranks of ``group``.
 
     ``signal`` is read on rank 0 only (other ranks may pass None).  Returns, on rank 0, a dict with the
     full SoA match arrays (numpy), ``pool`` (numpy [n_domains, range_size]), n_ranges, range_size,
-    domain_step, original_len, and the per-rank blocks; other ranks return None.  ``embedding`` and
-    ``emb_dim`` as :func:`compress_sharded_start` (the same on every rank).  ``compact=True``: rank 0 keeps only the
+    domain_step, original_len, and the per-rank blocks; other ranks return None.  ``embedding``,
+    ``emb_dim`` and ``fit`` as :func:`compress_sharded_start` (the same on every rank).  ``compact=True``: rank 0 keeps only the
     domain rows that the gathered matches name (engine.compact_arrays, on its device, before the pool is copied to
     the host): ``pool`` is then [m, range_size], ``idx`` renumbered, ``kept`` the rows' original indices; a shard's
     own matches do not determine that set, so the other ranks do nothing more than without it.
@@ -288,7 +292,7 @@ def compress_sharded(signal: Optional[np.ndarray], tile_size: int, top_k: int, e
     if rank == 0:
         sig = torch.from_numpy(np.ascontiguousarray(signal, dtype=np.float32)).to(device)
     out = compress_sharded_device(sig, tile_size, top_k, energy_thresh, group, device, compute, embedding=embedding,
-                                  emb_dim=emb_dim)
+                                  emb_dim=emb_dim, fit=fit)
     if rank != 0:
         return None
     if out.get("empty") and "idx" not in out:

@@ -14,6 +14,7 @@ Reference map (``/root/reference/fractal.py``):
   linear top-K :535-541, 617-620                           → fwav_sim_topk (+ fwav_tie_check / fwav.ties for exact ties)
   the same stages on rows of emb_dim = 32 columns (:275)   → fwav_pool_embed_dim, fwav_prune_dim, fwav_sim_topk_dim, …
   _process_gpu_batch :757-850                              → fwav_affine
+  (no counterpart; opt-in) the same solve selecting by the stored tuple's error → fwav_affine_fit (fit="clipped")
   decompress_audio :1378-1473                              → fwav_decode
   (no counterpart; opt-in) the pool rows that :1414 reads   → fwav_compact_domains (compact_device / compact_arrays)
   (no counterpart call; opt-in) range_candidates_from_embedding :337-351, each range's own embedding as its query
@@ -29,8 +30,8 @@ import torch
 from . import _lib, geometry, stages, ties as _ties  # noqa: F401  geometry: re-exported
 from .nporder import zero_query_candidates  # noqa: F401  (Q11 rows; re-exported)
 from ._lib import FwavError, call, size_call
-from .stages import (EMB_DIMS, EMBEDDINGS, QUERIES, QUERY_RANGE_MAX_K, TIE_MODES, TIE_REC,  # noqa: F401  re-exported
-                     check_emb_dim, check_embedding, check_query, n_domains_for)
+from .stages import (EMB_DIMS, EMBEDDINGS, FITS, QUERIES, QUERY_RANGE_MAX_K, TIE_MODES, TIE_REC,  # noqa: F401  re-exported
+                     check_emb_dim, check_embedding, check_fit, check_query, n_domains_for)
 
 
 def require_device(device=None) -> torch.device:
@@ -182,7 +183,7 @@ def _compress_device(sig: torch.Tensor, tile_size: int, top_k: int, energy_thres
                      search: str = "f16", on_pool=None, blas_threads: Optional[int] = None,
                      tie_order: str = "numpy", defer_ties: bool = False,
                      sub_blocks: Optional[int] = None, embedding: str = "matrix",
-                     emb_dim: int = 16, query: str = "domain_row") -> DeviceCompressed:
+                     emb_dim: int = 16, query: str = "domain_row", fit: str = "reference") -> DeviceCompressed:
     """Run the compress hot path on ``sig`` (1-D float32 tensor on a HIP device).
 
     ``shard=(lo, hi)`` restricts candidate search and the affine solve to ranges ``[lo, hi)`` (the
@@ -219,6 +220,14 @@ def _compress_device(sig: torch.Tensor, tile_size: int, top_k: int, energy_thres
     scores in the sgemv order of ``blas_threads``, numpy's tie order, the affine solve.  There is no Q9 error then
     (n_ranges > n_domains is legal: the queries do not index the domain table).  ValueError with emb_dim=32 or
     top_k > 64.
+    ``fit="clipped"`` (opt-in; the default "reference" is the reference's solve, which picks the slot by the error of
+    the unclipped least-squares scale and clips the stored scale afterwards) clips each slot's scale to ±s_clip before
+    its offset and error are computed and picks the smallest such error, ties going to the smaller domain index and
+    then the unmirrored slot (fwav_affine_fit): ``err`` is then the error of exactly the stored (s, o), s is the
+    constrained least-squares scale, and the order of the candidates inside a row cannot change a match.  It sits
+    after the search, so it composes with every option above; the whole call — sub-blocks, a shard, the re-solve of
+    host-ranked tie rows, deferred or not — solves in the one mode.  The tie check tests the reference's error, so
+    ``tie_order="numpy"`` then ranks every K-th place tie on the host, as "numpy_sets" does (stages.tie_mode).
     """
     if sig.dim() != 1 or sig.dtype != torch.float32 or not sig.is_cuda:
         raise ValueError("compress_device expects a 1-D float32 device tensor")
@@ -238,6 +247,7 @@ def _compress_device(sig: torch.Tensor, tile_size: int, top_k: int, energy_thres
     dim = check_emb_dim(emb_dim, embedding)
     check_query(query, dim, k)
     stages.check_tie_order(tie_order)
+    check_fit(fit)
     threads = _ties.blas_threads() if blas_threads is None else int(blas_threads)
     _mark(events, "voiced_ranges")
     ranges = _voiced_ranges(sig, n, rs, energy_thresh, st)
@@ -300,7 +310,7 @@ def _compress_device(sig: torch.Tensor, tile_size: int, top_k: int, energy_thres
     err = torch.empty(m, dtype=torch.float32, device=dev)
     if m > 0:
         S = _Search(emb, emb16, nd, dim, xq, lo, k, threads, rs, rsh, pool, cand, (idx, s, o, sym, err),
-                    stages.clip32(s_clip), TIE_MODES[tie_order])
+                    stages.clip32(s_clip), stages.tie_mode(tie_order, fit), fit)
         _mark(events, "prune")
         zc = _zero_cand_device(nd, k, dev)
         stages.prune(rsh.data_ptr(), m, lo, rs, stages.prune_thr(energy_thresh), int(bool(fast_mode)), emb.data_ptr(),
@@ -383,7 +393,8 @@ def _compress_device(sig: torch.Tensor, tile_size: int, top_k: int, energy_thres
 class _Search:
     """What the search stages of one call share, bound once: the tables (``query``: None, or query="range"'s
     (qemb, qemb16, n_query_rows, seed_stride)), the shard [lo, lo + m) with its ranges, candidates and outputs
-    ``outs`` = (idx, s, o, sym, err), and ``tie_mode`` = TIE_MODES[tie_order]."""
+    ``outs`` = (idx, s, o, sym, err), ``tie_mode`` = stages.tie_mode(tie_order, fit), and ``fit`` (stages.FITS), the
+    mode of every affine solve of the call."""
 
     emb: torch.Tensor
     emb16: Optional[torch.Tensor]
@@ -400,6 +411,7 @@ class _Search:
     outs: tuple
     s_clip: float
     tie_mode: int
+    fit: str = "reference"
 
     @property
     def qemb(self) -> Optional[torch.Tensor]:
@@ -415,7 +427,7 @@ class _Search:
     def fix_kw(self) -> dict:
         """... and of its fix-up (apply_rows, resolve_rows)."""
         return dict(ranges=self.rsh, range_size=self.rs, pool=self.pool, k=self.k, s_clip=self.s_clip, cand=self.cand,
-                    outs=self.outs)
+                    outs=self.outs, fit=self.fit)
 
     def workspace_size(self, mq: int) -> int:
         return stages.topk_workspace_size(mq, self.nd, self.k, emb_dim=self.dim, f16=self.emb16 is not None)
@@ -427,8 +439,8 @@ class _Search:
                         query=None if q is None else (q[0].data_ptr(), _p(q[1]), q[2], q[3]))
 
     def affine(self, m, st) -> None:
-        call("fwav_affine", self.rsh.data_ptr(), m, self.rs, self.cand.data_ptr(), self.k, self.pool.data_ptr(), self.nd,
-             self.s_clip, *[t.data_ptr() for t in self.outs], st)
+        stages.affine(self.rsh.data_ptr(), m, self.rs, self.cand.data_ptr(), self.k, self.pool.data_ptr(), self.nd,
+                      self.s_clip, [t.data_ptr() for t in self.outs], st, fit=self.fit)
 
     def tie_check(self, m, ties, max_ties, resolve, st) -> None:
         stages.tie_check(self.rsh.data_ptr(), m, self.rs, self.cand.data_ptr(), self.k, self.pool.data_ptr(), self.nd,

@@ -104,9 +104,11 @@ class DeviceBuffer:
             pass
 
 
-def affine_batch(ranges: np.ndarray, cand: np.ndarray, pool: np.ndarray, s_clip: float = 16.0):
+def affine_batch(ranges: np.ndarray, cand: np.ndarray, pool: np.ndarray, s_clip: float = 16.0,
+                 fit: str = "reference"):
     """_process_gpu_batch (fractal.py:757-850) for a whole batch: ranges f32[B, rs], cand i32[B, K] (−1 padded),
-    pool f32[nd, rs] → (idx i32[B], s f32[B], o f32[B], sym u8[B], err f32[B])."""
+    pool f32[nd, rs] → (idx i32[B], s f32[B], o f32[B], sym u8[B], err f32[B]).  ``fit`` as :func:`compress`."""
+    stages.check_fit(fit)
     ranges = np.ascontiguousarray(ranges, np.float32)
     cand = np.ascontiguousarray(cand, np.int32)
     pool = np.ascontiguousarray(pool, np.float32)
@@ -115,8 +117,8 @@ def affine_batch(ranges: np.ndarray, cand: np.ndarray, pool: np.ndarray, s_clip:
     nd = pool.shape[0]
     dr, dc, dp = (DeviceBuffer.from_array(x) for x in (ranges, cand, pool))
     outs = [DeviceBuffer(4 * B), DeviceBuffer(4 * B), DeviceBuffer(4 * B), DeviceBuffer(B), DeviceBuffer(4 * B)]
-    call("fwav_affine", dr.value, B, rs, dc.value, K, dp.value, nd, stages.clip32(s_clip),
-         *[b.value for b in outs], None)
+    stages.affine(dr.value, B, rs, dc.value, K, dp.value, nd, stages.clip32(s_clip), [b.value for b in outs], None,
+                  fit=fit)
     call("fwav_stream_sync", None)
     return (outs[0].to_array(np.int32, B), outs[1].to_array(np.float32, B), outs[2].to_array(np.float32, B),
             outs[3].to_array(np.uint8, B), outs[4].to_array(np.float32, B))
@@ -145,7 +147,8 @@ def _i32(buf: DeviceBuffer, count: int) -> np.ndarray:
 
 def compress(signal: np.ndarray, tile_size: int, top_k: int, energy_thresh: float = 1e-4, fast_mode: bool = True,
              s_clip: float = 16.0, tie_order: str = "numpy", threads: int | None = None,
-             embedding: str = "matrix", emb_dim: int = 16, compact: bool = False) -> dict | None:
+             embedding: str = "matrix", emb_dim: int = 16, compact: bool = False,
+             fit: str = "reference") -> dict | None:
     """compress_audio's device pipeline (fractal.py:1040-1256) with HIP buffers only, on the null stream:
 
       fwav_voiced_ranges → fwav_weighted_energy (silent test, :1083) → fwav_pool_embed → fwav_prune → fwav_sim_topk
@@ -164,9 +167,13 @@ def compress(signal: np.ndarray, tile_size: int, top_k: int, energy_thresh: floa
     scalars (the voiced thresholds, the prune threshold, the silent test).
     ``compact=True`` ends the sequence with fwav_compact_domains: ``pool`` then holds only the m rows that the matches
     name (f32[m, rs], ascending original index), ``idx`` is renumbered to them, ``n_domains`` = m, and ``kept``
-    i32[m] gives each row's original index (``emb`` and ``cand`` keep the original numbering)."""
+    i32[m] gives each row's original index (``emb`` and ``cand`` keep the original numbering).
+    ``fit="clipped"`` (fwav.engine.compress_device) solves every match, the tie rows' re-solve included, through
+    fwav_affine_fit: the slot whose stored tuple (s clipped to ±s_clip before o and err) fits best; ``tie_order="numpy"``
+    then ranks every K-th place tie (stages.tie_mode)."""
     dim = stages.check_emb_dim(emb_dim, embedding)
     stages.check_tie_order(tie_order)
+    stages.check_fit(fit)
     sig = np.ascontiguousarray(signal, np.float32).reshape(-1)
     n = sig.size
     if n == 0:
@@ -212,12 +219,12 @@ def compress(signal: np.ndarray, tile_size: int, top_k: int, energy_thresh: floa
                     d_ties.value, d_wsk.value, wsk, None, emb_dim=dim)
     outs = [DeviceBuffer(4 * nr), DeviceBuffer(4 * nr), DeviceBuffer(4 * nr), DeviceBuffer(nr), DeviceBuffer(4 * nr)]
     sc = stages.clip32(s_clip)
-    call("fwav_affine", d_ranges.value, nr, rs, d_cand.value, k, d_pool.value, nd, sc, *[b.value for b in outs], None)
+    stages.affine(d_ranges.value, nr, rs, d_cand.value, k, d_pool.value, nd, sc, [b.value for b in outs], None, fit=fit)
     n_ties = n_res = 0
     if tie_order != "index":
         d_res = DeviceBuffer(4 * (nr + 1))
         stages.tie_check(d_ranges.value, nr, rs, d_cand.value, k, d_pool.value, nd, d_emb.value, 0, T, d_ties.value, nr,
-                         stages.TIE_MODES[tie_order], d_res.value, None, emb_dim=dim)
+                         stages.tie_mode(tie_order, fit), d_res.value, None, emb_dim=dim)
         n_ties = int(_i32(d_ties, 1)[0])
         res = _i32(d_res, 1 + nr)
         n_res = int(res[0])
@@ -235,7 +242,7 @@ def compress(signal: np.ndarray, tile_size: int, top_k: int, energy_thresh: floa
             tmp = [DeviceBuffer(4 * n_res), DeviceBuffer(4 * n_res), DeviceBuffer(4 * n_res), DeviceBuffer(n_res),
                    DeviceBuffer(4 * n_res)]
             stages.tie_fixup(d_rows.value, n_res, d_newc.value, k, d_cand.value, d_ranges.value, rs, d_rsub.value,
-                             [b.value for b in tmp], [b.value for b in outs], d_pool.value, nd, sc, None)
+                             [b.value for b in tmp], [b.value for b in outs], d_pool.value, nd, sc, None, fit=fit)
     kept, nd_out = None, nd
     if compact:
         # after the tie fix-ups (they change idx): only the rows that the matches name, indices renumbered in place

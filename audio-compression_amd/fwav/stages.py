@@ -34,6 +34,10 @@ QUERY_RANGE_MAX_K = 64
 #: tie_order → fwav_tie_check's exact_sets argument ("index" never calls it)
 TIE_MODES = {"numpy": 0, "numpy_sets": 1, "numpy_rows": 2, "index": -1}
 TIE_REC = 9  # int32 per tie record (kTieRec, fwav_common.h)
+#: fit → fwav_affine_fit's fit argument: "reference" selects the slot by the error of the unclipped least-squares
+#: scale and clips the stored one afterwards (fractal.py:804-824); "clipped" clips first, so that the error it selects
+#: by and stores is the stored tuple's, and breaks ties by (domain, orientation) instead of the slot
+FITS = ("reference", "clipped")
 
 
 def check_embedding(embedding: str, rs: int) -> str:
@@ -77,6 +81,24 @@ def check_tie_order(tie_order: str) -> str:
                          " match), 'numpy_sets' (and wherever it decides a candidate set), 'numpy_rows' (and wherever it"
                          " decides a candidate row's order) or 'index'")
     return tie_order
+
+
+def check_fit(fit: str) -> str:
+    """``fit`` validated (no device work): ValueError for a name other than "reference" and "clipped"."""
+    if fit not in FITS:
+        raise ValueError(f"fit must be 'reference' or 'clipped', not {fit!r}")
+    return fit
+
+
+def tie_mode(tie_order: str, fit: str = "reference") -> int:
+    """fwav_tie_check's exact_sets for ``tie_order`` under ``fit``.  The check tests the reference's error, so with
+    fit="clipped" it cannot tell which K-th place ties leave the match alone: "numpy" then ranks every one of them on
+    the host ("numpy_sets"), which makes the candidate sets the reference's; the order inside a set cannot change a
+    clipped match."""
+    check_tie_order(tie_order)
+    if check_fit(fit) == "clipped" and tie_order == "numpy":
+        return TIE_MODES["numpy_sets"]
+    return TIE_MODES[tie_order]
 
 
 # ------------------------------------------------------------------------------------------ the reference's scalars
@@ -224,12 +246,20 @@ def score_rows(emb, nd, rows, n_rows, q_offset, threads, scores, stream, *, emb_
         call("fwav_score_rows", emb, nd, rows, n_rows, q_offset, threads, scores, stream)
 
 
-def tie_fixup(rows, n, new_cand, k, cand, ranges, rs, rsub, tmp5, outs5, pool, nd, s_clip, stream):
+def affine(ranges, n, rs, cand, k, pool, nd, s_clip, outs5, stream, *, fit="reference"):
+    """_process_gpu_batch (fractal.py:757-850) into ``outs5`` = (idx, s, o, sym, err); ``fit``: FITS."""
+    if fit == "reference":
+        call("fwav_affine", ranges, n, rs, cand, k, pool, nd, s_clip, *outs5, stream)
+    else:
+        call("fwav_affine_fit", ranges, n, rs, cand, k, pool, nd, s_clip, *outs5, FITS.index(check_fit(fit)), stream)
+
+
+def tie_fixup(rows, n, new_cand, k, cand, ranges, rs, rsub, tmp5, outs5, pool, nd, s_clip, stream, *, fit="reference"):
     """numpy's candidate rows written back and their matches re-solved, three launches: ``new_cand`` scattered into
-    ``cand`` and the rows' ranges gathered into ``rsub``, the affine solve of those n rows into ``tmp5``, its outputs
-    scattered into ``outs5`` = (idx, s, o, sym, err)."""
+    ``cand`` and the rows' ranges gathered into ``rsub``, the affine solve of those n rows (in the call's own ``fit``)
+    into ``tmp5``, its outputs scattered into ``outs5`` = (idx, s, o, sym, err)."""
     call("fwav_tie_rows_in", rows, n, new_cand, k, cand, ranges, rs, rsub, stream)
-    call("fwav_affine", rsub, n, rs, new_cand, k, pool, nd, s_clip, *tmp5, stream)
+    affine(rsub, n, rs, new_cand, k, pool, nd, s_clip, tmp5, stream, fit=fit)
     call("fwav_tie_rows_out", rows, n, *tmp5, *outs5, stream)
 
 

@@ -261,9 +261,11 @@ def rank_rows_async(rows: torch.Tensor, *, emb: torch.Tensor, n_domains: int, q_
 
 
 def apply_rows(rows: torch.Tensor, futs: list, *, ranges: torch.Tensor, range_size: int, pool: torch.Tensor,
-               n_domains: int, k: int, s_clip: float, cand: torch.Tensor, outs: tuple, stream: int) -> None:
+               n_domains: int, k: int, s_clip: float, cand: torch.Tensor, outs: tuple, stream: int,
+               fit: str = "reference") -> None:
     """Write numpy's candidate rows (the futures of rank_rows) into ``cand`` and re-run the affine solve for those
-    rows into ``outs`` = (idx, s, o, sym, err), on the current stream (``stream``)."""
+    rows (in the call's ``fit``, fwav.stages.FITS) into ``outs`` = (idx, s, o, sym, err), on the current stream
+    (``stream``)."""
     dev = rows.device
     n = rows.numel()
     # through page-locked memory, asynchronously: a copy from pageable memory would first wait for everything queued
@@ -275,12 +277,13 @@ def apply_rows(rows: torch.Tensor, futs: list, *, ranges: torch.Tensor, range_si
     tmp = [torch.empty(n, dtype=t.dtype, device=dev) for t in outs]
     stages.tie_fixup(rows.data_ptr(), n, newc.data_ptr(), k, cand.data_ptr(), ranges.data_ptr(), rs, rsub.data_ptr(),
                      [t.data_ptr() for t in tmp], [t.data_ptr() for t in outs], pool.data_ptr(), int(n_domains),
-                     float(s_clip), stream)
+                     float(s_clip), stream, fit=fit)
 
 
 def resolve_rows(rows: torch.Tensor, *, emb: torch.Tensor, n_domains: int, q_offset: int, k: int, threads: int,
                  ranges: torch.Tensor, range_size: int, pool: torch.Tensor, s_clip: float, cand: torch.Tensor,
-                 outs: tuple, stream: int, emb_dim: int = 16, qemb: torch.Tensor | None = None) -> None:
+                 outs: tuple, stream: int, emb_dim: int = 16, qemb: torch.Tensor | None = None,
+                 fit: str = "reference") -> None:
     """Rows (local indices, device int32) whose match depends on numpy's tie order: exact score rows in launches of up
     to DEVICE_ROW_BUDGET (fwav_score_rows reads the embedding table once per launch), copied to a ring of page-locked
     row slots (HOST_ROW_BUDGET), numpy's ranking of each row on a host thread pool as soon as it lands, the new
@@ -301,4 +304,4 @@ def resolve_rows(rows: torch.Tensor, *, emb: torch.Tensor, n_domains: int, q_off
         print(f"fwav.ties: {n} rows x {n_domains}: {(time.perf_counter() - t0) * 1e3:.1f} ms (device score rows + "
               f"copies {(t1 - t0) * 1e3:.1f} ms, numpy tail {(time.perf_counter() - t1) * 1e3:.1f} ms)", flush=True)
     apply_rows(rows, futs, ranges=ranges, range_size=range_size, pool=pool, n_domains=n_domains, k=k, s_clip=s_clip,
-               cand=cand, outs=outs, stream=stream)
+               cand=cand, outs=outs, stream=stream, fit=fit)

@@ -158,6 +158,15 @@ int fwav_score_rows(const float* emb, int64_t n_domains, const int32_t* rows, in
 int fwav_affine(const float* ranges, int64_t n_ranges, int range_size, const int32_t* cand, int k, const float* pool,
                 int64_t n_domains, float s_clip, int32_t* out_idx, float* out_s, float* out_o, uint8_t* out_sym,
                 float* out_err, void* stream);
+/* fwav_affine with a fit mode.  fit 0 is fwav_affine itself.  fit 1 ("clipped"; no counterpart in the reference)
+ * selects by the error of the tuple it stores: per slot s = clip(Σd̃r̃/(Σd̃²+1e-12), ±|s_clip|) (np.clip: NaN stays
+ * NaN), o = r̄ − s·d̄ and err = ‖s·D+o−R‖₂ from that s (+inf for cand < 0); the winner is the first NaN error, else
+ * the smallest error, then the smaller clamped domain index, then unmirrored before mirrored — the order of the
+ * candidates inside a row cannot change it.  Outputs as fwav_affine's, err being the error of exactly (s, o).  Any
+ * other fit: FWAV_ERR_ARG before any device work. */
+int fwav_affine_fit(const float* ranges, int64_t n_ranges, int range_size, const int32_t* cand, int k,
+                    const float* pool, int64_t n_domains, float s_clip, int32_t* out_idx, float* out_s, float* out_o,
+                    uint8_t* out_sym, float* out_err, int fit, void* stream);
 /* Tie check (after fwav_affine on the same rows): for every query listed in ties (fwav_sim_topk), decide whether the
  * reference's numpy tie order could change its match (fractal.py:816-824) — equal scores inside the top K when two
  * candidates of one run of equal scores both attain the minimum error; a tie at the K-th place when some member of

@@ -1,7 +1,9 @@
-"""compress_audio(query="range") measured against the default query="domain_row" (DESIGN §3.8), one JSON line each.
+"""compress_audio(query="range") measured against the default query="domain_row" (DESIGN §3.8), and fit="clipped"
+against the default fit="reference" (DESIGN §3.9), one JSON line each.
 
 usage: python tools/bench_query.py search  [--config cfg2] [--reps 20] [--warmup 3] [--seconds S]
        python tools/bench_query.py quality
+       python tools/bench_query.py fit     [--config cfg2] [--reps 20] [--warmup 3] [--seconds S]
 
 search: the similarity search alone at a bench configuration's shape, by HIP events as tools/bench_embdim.py does it —
   one compress_device(query="range") call builds the domain table, the ranges' own embeddings and the active list; then
@@ -11,8 +13,12 @@ search: the similarity search alone at a bench configuration's shape, by HIP eve
   product's geometry with its floor (tools/first_stats.py's): level-2 (tile, set) pairs per query set and appends per
   query — whether the centroid filter's premise (neighbouring queries are close) survives disjoint ranges.
 quality: the four signals of tests/test_gpu_query_range.py::test_fit_snr_gains_at_least_3_db (K = 32) under both
-  queries: the encoder's fit SNR 10·log10(Σ‖r‖² / Σ err²) over the searched ranges, and the decoded SNR of
-  decompress_audio at s_damping = 0 and 1e-6 against the voiced-masked input."""
+  queries and both fits: the encoder's fit SNR 10·log10(Σ‖r‖² / Σ err²) over the searched ranges, and the decoded SNR
+  of decompress_audio at s_damping = 0 and 1e-6 against the voiced-masked input, over the whole signal and over the
+  searched ranges alone (the figure the fit SNR promises).
+fit: at a bench configuration's shape, in one process: fwav_affine_fit in reference and in clipped mode on the call's
+  own candidate rows, launched alternately (medians of HIP events); then whole compress_device calls under
+  tie_order="numpy" with each fit — the rows ranked on the host and the wall time per call."""
 import argparse
 import json
 import os
@@ -118,28 +124,71 @@ def quality(args):
                "noise(1.0, 44100) tile 2048": (synth.noise(1.0, 44100), 2048)}
     for name, (sig, tile) in signals.items():
         row = dict(what="quality", signal=name)
-        for q in ("domain_row", "range"):
-            r = engine.compress_device(torch.from_numpy(sig).to(dev), tile, 32, keep_intermediates=True, query=q)
+        for q, fit in ((q, f) for q in ("domain_row", "range") for f in ("reference", "clipped")):
+            r = engine.compress_device(torch.from_numpy(sig).to(dev), tile, 32, keep_intermediates=True, query=q,
+                                       fit=fit)
             torch.cuda.synchronize()
             rs = r.range_size
             ranges = r.ranges.cpu().numpy().reshape(-1, rs)
             err = r.err.cpu().numpy()
             ok = np.isfinite(err)
-            row[q] = dict(fit_snr_db=float(10 * np.log10((ranges[ok].astype(np.float64) ** 2).sum()
-                                                         / (err[ok].astype(np.float64) ** 2).sum())),
-                          mean_err=float(err[ok].mean()))
+            sig2 = (ranges[ok].astype(np.float64) ** 2).sum()
+            col = row[f"{q}/{fit}"] = dict(query=q, fit=fit, mean_err=float(err[ok].mean()),
+                                           fit_snr_db=float(10 * np.log10(sig2 / (err[ok].astype(np.float64) ** 2).sum())))
             masked = ranges.reshape(-1)[:len(sig)]
             for d in (0.0, 1e-6):
                 rec, ran, _ = engine.decompress_device(r.idx, r.s, r.o, r.sym, r.pool, r.n_ranges, rs, s_damping=d)
-                row[q][f"decoded_snr_db_s_damping_{d:g}"] = float(api.compute_snr(masked, rec.cpu().numpy()[:len(sig)]))
-                row[q][f"iterations_s_damping_{d:g}"] = ran
+                rec = rec.cpu().numpy()
+                col[f"decoded_snr_db_s_damping_{d:g}"] = float(api.compute_snr(masked, rec[:len(sig)]))
+                noise = ((rec.reshape(-1, rs)[ok].astype(np.float64) - ranges[ok]) ** 2).sum()
+                col[f"decoded_searched_snr_db_s_damping_{d:g}"] = float(10 * np.log10(sig2 / noise))
+                col[f"iterations_s_damping_{d:g}"] = ran
         row["n_ranges"], row["n_domains"] = r.n_ranges, r.n_domains
         print(json.dumps(row), flush=True)
 
 
+def fit(args):
+    import time
+
+    from fwav import engine, stages, synth
+    cfg = synth.CONFIGS[args.config]
+    tile, K = cfg["tile"], cfg["top_k"]
+    sig_h, _, _ = synth.make_config_signal(args.config, seconds=args.seconds, seed=0)
+    dev = torch.device("cuda", 0)
+    sig = torch.from_numpy(sig_h).to(dev)
+    r = engine.compress_device(sig, tile, K, keep_intermediates=True)
+    torch.cuda.synchronize()
+    nd, nq, rs = r.n_domains, r.n_ranges, r.range_size
+    st = torch.cuda.current_stream(dev).cuda_stream
+    outs = {f: [torch.empty(nq, dtype=t.dtype, device=dev) for t in (r.idx, r.s, r.o, r.sym, r.err)]
+            for f in stages.FITS}
+
+    def solve(f):
+        return lambda: stages.affine(r.ranges.data_ptr(), nq, rs, r.cand.data_ptr(), K, r.pool.data_ptr(), nd, 16.0,
+                                     [t.data_ptr() for t in outs[f]], st, fit=f)
+
+    (t_ref, t_clip), spread = _median_ms([solve("reference"), solve("clipped")], args.reps, args.warmup)
+    changed = int(((outs["reference"][0] != outs["clipped"][0]) | (outs["reference"][3] != outs["clipped"][3])).sum())
+    print(json.dumps(dict(what="fit affine", config=args.config, n_ranges=nq, n_domains=nd, top_k=K, range_size=rs,
+                          reference_ms=t_ref, clipped_ms=t_clip, ratio=t_clip / t_ref, min_max_ms=spread,
+                          matches_changed=changed)), flush=True)
+    for f in stages.FITS:
+        wall = []
+        for it in range(args.warmup + max(args.reps // 4, 3)):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            x = engine.compress_device(sig, tile, K, tie_order="numpy", fit=f)
+            torch.cuda.synchronize()
+            if it >= args.warmup:
+                wall.append((time.perf_counter() - t0) * 1e3)
+        print(json.dumps(dict(what="fit ties", config=args.config, fit=f, tie_order="numpy", rows_with_exact_ties=x.n_ties,
+                              rows_ranked_by_numpy=x.n_resolved, call_ms_median=float(np.median(wall)),
+                              call_ms_min_max=(float(min(wall)), float(max(wall))))), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("what", choices=("search", "quality"))
+    ap.add_argument("what", choices=("search", "quality", "fit"))
     ap.add_argument("--config", default="cfg2")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
@@ -147,7 +196,7 @@ def main():
     args = ap.parse_args()
     import __graft_entry__
     __graft_entry__.build()
-    (search if args.what == "search" else quality)(args)
+    {"search": search, "quality": quality, "fit": fit}[args.what](args)
 
 
 if __name__ == "__main__":
