@@ -21,7 +21,19 @@
 // — the constrained least-squares scale for |s| ≤ |s_clip| — and the winner is the first NaN error, else the smallest
 // error, then the smaller clamped domain index, then unmirrored before mirrored: a function of the candidate set, not
 // of the candidates' order.  Slots that tie in all three hold the same tile in the same orientation, so the same
-// tuple.  The reference instantiations compile to the code they were before the parameter existed.
+// tuple.
+//
+// Layout.  The fit is stated once per operand form, and a change to it is made in these three functions:
+//   fit_any<FIT>          one orientation, run-time length, operands in memory   (k_affine_any, pair_errors<0>)
+//   eval_orient<RS, FIT>  one orientation, fixed length, operands in registers   (k_affine, pair_errors<RS>)
+//   affine_one<RS, FIT>   both orientations packed, fixed length                 (k_affine_batch, the hot path)
+// Everything around it is stated once: gather_row (a tile into registers), FitOrder<FIT> (the tie-break key of a slot
+// and the order the winner is the minimum of), wave_best / store_best (the scalar solvers' reduction and output) and
+// the one tail of affine_one (the packed solver's).  k_tie_check follows with pair_errors, which always fits in
+// kFitReference: the check is a statement about the reference's error.  Then the gather diagnostic, the tie-row
+// kernels and the C ABI, where affine_launch and tie_check_launch each name every instantiation once.
+#include <type_traits>
+
 #include "fwav_common.h"
 #include "../../include/fwav.h"
 
@@ -37,30 +49,53 @@ constexpr int kFitReference = 0, kFitClipped = 1;
 
 struct Best {
   float err, s, o;
-  int slot, dom;
+  int slot, dom;  // slot: the slot's FitOrder key
 };
 
-__device__ __forceinline__ bool better(float e1, int s1, float e2, int s2) {
+// (e1, k1) before (e2, k2) in the reference's argmin order: the first NaN error, else the smaller error, else the
+// smaller key
+template <class Key>
+__device__ __forceinline__ bool first_min(float e1, Key k1, float e2, Key k2) {
   const bool n1 = e1 != e1, n2 = e2 != e2;
-  if (n1 || n2) return (n1 && n2) ? s1 < s2 : n1;
-  return e1 < e2 || (e1 == e2 && s1 < s2);
+  if (n1 || n2) return (n1 && n2) ? k1 < k2 : n1;
+  return e1 < e2 || (e1 == e2 && k1 < k2);
 }
 
-// better() with the tie-break keys compared as u32: kFitClipped's key is domain·2 + mirrored (kFitReference's: the slot)
-__device__ __forceinline__ bool better_key(float e1, int k1, float e2, int k2) {
-  const uint32_t u1 = (uint32_t)k1, u2 = (uint32_t)k2;
-  const bool n1 = e1 != e1, n2 = e2 != e2;
-  if (n1 || n2) return (n1 && n2) ? u1 < u2 : n1;
-  return e1 < e2 || (e1 == e2 && u1 < u2);
-}
-// (macros, not wrappers: the reference instantiations then hold the very calls they held before)
-#define FWAV_BETTER(e1, k1, e2, k2) (FIT == kFitClipped ? better_key(e1, k1, e2, k2) : better(e1, k1, e2, k2))
-#define FWAV_FIT_KEY(slot, di, mirrored) \
-  (FIT == kFitClipped ? (int)((uint32_t)(di) * 2u + (uint32_t)(mirrored)) : (slot))
-// the key no slot has: it loses every tie
+// The selection order of a fit mode.  kFitReference: the key is the slot (first minimum over [K | K mirrored]).
+// kFitClipped: domain·2 + mirrored, compared as u32 (Best carries it in an int).
 template <int FIT>
-constexpr int kNoSlot = FIT == kFitClipped ? -1 : 0x7fffffff;
+struct FitOrder {
+  using Key = std::conditional_t<FIT == kFitClipped, uint32_t, int>;
+  static constexpr int none = FIT == kFitClipped ? -1 : 0x7fffffff;  // the key no slot has: it loses every tie
+  static __device__ __forceinline__ int key(int slot, int32_t dom, int mirrored) {
+    if constexpr (FIT == kFitClipped) return (int)((uint32_t)dom * 2u + (uint32_t)mirrored);
+    return slot;
+  }
+  static __device__ __forceinline__ bool better(float e1, int k1, float e2, int k2) {
+    return first_min<Key>(e1, (Key)k1, e2, (Key)k2);
+  }
+  static __device__ __forceinline__ bool mirrored(int key, int K) {
+    return FIT == kFitClipped ? (key & 1) != 0 : key >= K;
+  }
+};
 
+// Tile `di` (a row index, already clamped to ≥ 0) of the pool into registers.
+template <int RS>
+__device__ __forceinline__ void gather_row(const float* __restrict__ pool, int64_t di, float (&D)[RS]) {
+  if constexpr (RS % 4 == 0) {
+    const float4* p = reinterpret_cast<const float4*>(pool + di * RS);
+#pragma unroll
+    for (int j = 0; j < RS / 4; ++j) {
+      const float4 v = p[j];
+      D[4 * j] = v.x; D[4 * j + 1] = v.y; D[4 * j + 2] = v.z; D[4 * j + 3] = v.w;
+    }
+  } else {
+#pragma unroll
+    for (int i = 0; i < RS; ++i) D[i] = pool[di * RS + i];
+  }
+}
+
+// The fit of one orientation X of a tile against range R (rc = R − rm), fixed length, operands in registers; c = |s_clip|.
 template <int RS, int FIT = kFitReference>
 __device__ __forceinline__ void eval_orient(const float (&X)[RS], const float (&R)[RS], const float (&rc)[RS], float rm,
                                             float& s, float& o, float& err, float c = 0.f) {
@@ -83,6 +118,58 @@ __device__ __forceinline__ void eval_orient(const float (&X)[RS], const float (&
   err = sqrtf(pw_sum_n<RS>(fe));
 }
 
+// The same fit at a run-time length n, operands read from memory: tile D as stored (orient 0) or mirrored (1) against
+// range R of mean rm; c = |s_clip|.
+template <int FIT>
+__device__ __forceinline__ void fit_any(const float* __restrict__ D, int orient, const float* __restrict__ R, float rm,
+                                        int n, float c, float& s_out, float& o_out, float& err) {
+  auto X = [&](int i) { return orient ? D[n - 1 - i] : D[i]; };
+  const float dm = pw_sum(X, n) / (float)n;
+  auto fn = [&](int i) { return (X(i) - dm) * (R[i] - rm); };
+  auto fd = [&](int i) {
+    const float t = X(i) - dm;
+    return t * t;
+  };
+  const float num = pw_sum(fn, n);
+  const float den = pw_sum(fd, n) + 1e-12f;
+  const float s = FIT == kFitClipped ? clip_sym(num / den, c) : num / den;
+  const float o = rm - s * dm;
+  auto fe = [&](int i) {
+    const float df = (s * X(i) + o) - R[i];
+    return df * df;
+  };
+  err = sqrtf(pw_sum(fe, n));
+  s_out = s;
+  o_out = o;
+}
+
+// The wave's best of every lane's: a 6-step xor-shuffle reduction in the mode's order; every lane ends with it.
+template <int FIT>
+__device__ __forceinline__ void wave_best(Best& b) {
+#pragma unroll
+  for (int m = 1; m < 64; m <<= 1) {
+    Best o;
+    o.err = __shfl_xor(b.err, m);
+    o.s = __shfl_xor(b.s, m);
+    o.o = __shfl_xor(b.o, m);
+    o.slot = __shfl_xor(b.slot, m);
+    o.dom = __shfl_xor(b.dom, m);
+    if (FitOrder<FIT>::better(o.err, o.slot, b.err, b.slot)) b = o;
+  }
+}
+
+template <int FIT>
+__device__ __forceinline__ void store_best(const Best& b, int64_t r, int K, float sc, int32_t* __restrict__ out_idx,
+                                           float* __restrict__ out_s, float* __restrict__ out_o,
+                                           uint8_t* __restrict__ out_sym, float* __restrict__ out_err) {
+  out_idx[r] = b.dom;
+  out_s[r] = clip_sym(b.s, sc);  // (kFitClipped: already clipped; the clip is idempotent)
+  out_o[r] = b.o;
+  out_sym[r] = (uint8_t)FitOrder<FIT>::mirrored(b.slot, K);
+  out_err[r] = b.err;
+}
+
+// K > 64 at rs 4, 8, 16: lane c takes candidates c, c + 64, …
 template <int RS, int FIT>
 __global__ __launch_bounds__(64 * kAffWaves) void k_affine(const float* __restrict__ ranges, int64_t nr,
                                                            const int32_t* __restrict__ cand, int K,
@@ -90,6 +177,7 @@ __global__ __launch_bounds__(64 * kAffWaves) void k_affine(const float* __restri
                                                            int32_t* __restrict__ out_idx, float* __restrict__ out_s,
                                                            float* __restrict__ out_o, uint8_t* __restrict__ out_sym,
                                                            float* __restrict__ out_err) {
+  using Ord = FitOrder<FIT>;
   const int lane = threadIdx.x & 63;
   const int64_t r = (int64_t)blockIdx.x * kAffWaves + (threadIdx.x >> 6);
   if (r >= nr) return;
@@ -102,57 +190,32 @@ __global__ __launch_bounds__(64 * kAffWaves) void k_affine(const float* __restri
   for (int i = 0; i < RS; ++i) rc[i] = R[i] - rm;
 
   const float sc = fabsf(s_clip);
-  Best b{INFINITY, 0.f, 0.f, kNoSlot<FIT>, 0};
+  Best b{INFINITY, 0.f, 0.f, Ord::none, 0};
   bool have = false;
   const int32_t* cr = cand + r * (int64_t)K;
   for (int c = lane; c < K; c += 64) {
     const int32_t ci = cr[c];
     const int32_t di = ci < 0 ? 0 : ci;
     float D[RS], M[RS];
-    if constexpr (RS % 4 == 0) {
-      const float4* p = reinterpret_cast<const float4*>(pool + (int64_t)di * RS);
-#pragma unroll
-      for (int j = 0; j < RS / 4; ++j) {
-        float4 v = p[j];
-        D[4 * j] = v.x; D[4 * j + 1] = v.y; D[4 * j + 2] = v.z; D[4 * j + 3] = v.w;
-      }
-    } else {
-#pragma unroll
-      for (int i = 0; i < RS; ++i) D[i] = pool[(int64_t)di * RS + i];
-    }
+    gather_row<RS>(pool, di, D);
 #pragma unroll
     for (int i = 0; i < RS; ++i) M[i] = D[RS - 1 - i];
     float s0, o0, e0, s1, o1, e1;
     eval_orient<RS, FIT>(D, R, rc, rm, s0, o0, e0, sc);
     eval_orient<RS, FIT>(M, R, rc, rm, s1, o1, e1, sc);
     if (ci < 0) { e0 = INFINITY; e1 = INFINITY; }
-    if (!have || FWAV_BETTER(e0, FWAV_FIT_KEY(c, di, 0), b.err, b.slot)) {
-      b = Best{e0, s0, o0, FWAV_FIT_KEY(c, di, 0), di};
+    const int k0 = Ord::key(c, di, 0), k1 = Ord::key(K + c, di, 1);
+    if (!have || Ord::better(e0, k0, b.err, b.slot)) {
+      b = Best{e0, s0, o0, k0, di};
       have = true;
     }
-    if (FWAV_BETTER(e1, FWAV_FIT_KEY(K + c, di, 1), b.err, b.slot))
-      b = Best{e1, s1, o1, FWAV_FIT_KEY(K + c, di, 1), di};
+    if (Ord::better(e1, k1, b.err, b.slot)) b = Best{e1, s1, o1, k1, di};
   }
-#pragma unroll
-  for (int m = 1; m < 64; m <<= 1) {
-    Best o;
-    o.err = __shfl_xor(b.err, m);
-    o.s = __shfl_xor(b.s, m);
-    o.o = __shfl_xor(b.o, m);
-    o.slot = __shfl_xor(b.slot, m);
-    o.dom = __shfl_xor(b.dom, m);
-    if (FWAV_BETTER(o.err, o.slot, b.err, b.slot)) b = o;
-  }
-  if (lane == 0) {
-    out_idx[r] = b.dom;
-    out_s[r] = clip_sym(b.s, sc);  // (kFitClipped: already clipped; the clip is idempotent)
-    out_o[r] = b.o;
-    out_sym[r] = (uint8_t)(FIT == kFitClipped ? (b.slot & 1) : (b.slot >= K));
-    out_err[r] = b.err;
-  }
+  wave_best<FIT>(b);
+  if (lane == 0) store_best<FIT>(b, r, K, sc, out_idx, out_s, out_o, out_sym, out_err);
 }
 
-// Generic rs (runtime), rows read from global memory; same arithmetic.
+// Any other rs (run-time), rows read from global memory; same arithmetic.
 template <int FIT>
 __global__ __launch_bounds__(64 * kAffWaves) void k_affine_any(const float* __restrict__ ranges, int64_t nr, int rs,
                                                                const int32_t* __restrict__ cand, int K,
@@ -160,13 +223,15 @@ __global__ __launch_bounds__(64 * kAffWaves) void k_affine_any(const float* __re
                                                                int32_t* __restrict__ out_idx, float* __restrict__ out_s,
                                                                float* __restrict__ out_o, uint8_t* __restrict__ out_sym,
                                                                float* __restrict__ out_err) {
+  using Ord = FitOrder<FIT>;
   const int lane = threadIdx.x & 63;
   const int64_t r = (int64_t)blockIdx.x * kAffWaves + (threadIdx.x >> 6);
   if (r >= nr) return;
   const float* R = ranges + r * rs;
   auto fr = [&](int i) { return R[i]; };
   const float rm = pw_sum(fr, rs) / (float)rs;
-  Best b{INFINITY, 0.f, 0.f, kNoSlot<FIT>, 0};
+  const float sc = fabsf(s_clip);
+  Best b{INFINITY, 0.f, 0.f, Ord::none, 0};
   bool have = false;
   const int32_t* cr = cand + r * (int64_t)K;
   for (int c = lane; c < K; c += 64) {
@@ -174,49 +239,16 @@ __global__ __launch_bounds__(64 * kAffWaves) void k_affine_any(const float* __re
     const int32_t di = ci < 0 ? 0 : ci;
     const float* D = pool + (int64_t)di * rs;
     for (int orient = 0; orient < 2; ++orient) {
-      auto X = [&](int i) { return orient ? D[rs - 1 - i] : D[i]; };
-      const float dm = pw_sum(X, rs) / (float)rs;
-      auto fn = [&](int i) { return (X(i) - dm) * (R[i] - rm); };
-      auto fd = [&](int i) {
-        const float t = X(i) - dm;
-        return t * t;
-      };
-      const float num = pw_sum(fn, rs);
-      const float den = pw_sum(fd, rs) + 1e-12f;
-      const float s = FIT == kFitClipped ? clip_sym(num / den, fabsf(s_clip)) : num / den;
-      const float o = rm - s * dm;
-      auto fe = [&](int i) {
-        const float df = (s * X(i) + o) - R[i];
-        return df * df;
-      };
-      float e = sqrtf(pw_sum(fe, rs));
+      float s, o, e;
+      fit_any<FIT>(D, orient, R, rm, rs, sc, s, o, e);
       if (ci < 0) e = INFINITY;
-      const int slot = FWAV_FIT_KEY(orient * K + c, di, orient);
-      if (!have || FWAV_BETTER(e, slot, b.err, b.slot)) { b = Best{e, s, o, slot, di}; have = true; }
+      const int key = Ord::key(orient * K + c, di, orient);
+      if (!have || Ord::better(e, key, b.err, b.slot)) { b = Best{e, s, o, key, di}; have = true; }
     }
   }
-#pragma unroll
-  for (int m = 1; m < 64; m <<= 1) {
-    Best o;
-    o.err = __shfl_xor(b.err, m);
-    o.s = __shfl_xor(b.s, m);
-    o.o = __shfl_xor(b.o, m);
-    o.slot = __shfl_xor(b.slot, m);
-    o.dom = __shfl_xor(b.dom, m);
-    if (FWAV_BETTER(o.err, o.slot, b.err, b.slot)) b = o;
-  }
-  if (lane == 0) {
-    out_idx[r] = b.dom;
-    out_s[r] = clip_sym(b.s, fabsf(s_clip));
-    out_o[r] = b.o;
-    out_sym[r] = (uint8_t)(FIT == kFitClipped ? (b.slot & 1) : (b.slot >= K));
-    out_err[r] = b.err;
-  }
+  wave_best<FIT>(b);
+  if (lane == 0) store_best<FIT>(b, r, K, sc, out_idx, out_s, out_o, out_sym, out_err);
 }
-
-
-#undef FWAV_BETTER
-#undef FWAV_FIT_KEY
 
 // ------------------------------------------------------------------ batched kernel (K <= 64, rs 4/8/16)
 // Lane c ↔ candidate c; a wave handles kAffBatch consecutive ranges.  Per range the work is two dependent
@@ -229,22 +261,6 @@ __global__ __launch_bounds__(64 * kAffWaves) void k_affine_any(const float* __re
 // op.  The argmin is two DPP wave reductions on (NaN-first error order, slot) followed by readlanes of the
 // winner, instead of a 5-value shuffle tree.  kFitClipped: the second reduction is over domain·2 + mirrored, which
 // several lanes can hold (one domain twice in a row), so the winning lane is the first of a ballot.
-template <int RS>
-__device__ __forceinline__ void gather_row(const float* __restrict__ pool, int32_t ci, float (&D)[RS]) {
-  const int64_t di = ci < 0 ? 0 : ci;
-  if constexpr (RS % 4 == 0) {
-    const float4* p = reinterpret_cast<const float4*>(pool + di * RS);
-#pragma unroll
-    for (int j = 0; j < RS / 4; ++j) {
-      const float4 v = p[j];
-      D[4 * j] = v.x; D[4 * j + 1] = v.y; D[4 * j + 2] = v.z; D[4 * j + 3] = v.w;
-    }
-  } else {
-#pragma unroll
-    for (int i = 0; i < RS; ++i) D[i] = pool[di * RS + i];
-  }
-}
-
 extern "C" __device__ uint32_t __ockl_wfred_min_u32(uint32_t);
 
 template <int RS, int FIT>
@@ -281,42 +297,34 @@ __device__ __forceinline__ void affine_one(const float (&R)[RS], int64_t r, int3
   const f32x2 ss = pw_sum_n<RS>(fe);
   float e0 = sqrtf(ss.x), e1 = sqrtf(ss.y);
   if (ci < 0) { e0 = INFINITY; e1 = INFINITY; }
-  // lane-local best of slot `lane` and slot K + lane (first minimum, NaN first), then the wave's
-  const bool take1 = better(e1, K + lane, e0, lane);
+  // lane-local best of slot `lane` and slot K + lane (first minimum, NaN first; in either mode: the two slots hold
+  // one domain, so kFitClipped's order of them is the slots'), then the wave's by two reductions: the error key, then
+  // among its holders the mode's key
+  const bool take1 = first_min(e1, K + lane, e0, lane);
   const float eb = take1 ? e1 : e0;
   const uint32_t slot = take1 ? (uint32_t)(K + lane) : (uint32_t)lane;
   const uint32_t ekey = has ? ((eb != eb) ? 0u : __float_as_uint(eb) + 1u) : 0xffffffffu;
   const uint32_t kmin = __ockl_wfred_min_u32(ekey);
-  if constexpr (FIT == kFitClipped) {
-    // (err key, domain·2 + mirrored): the lane's two slots hold one domain, so its own best is the one above
-    const uint32_t dkey = (uint32_t)(ci < 0 ? 0 : ci) * 2u + (take1 ? 1u : 0u);
-    const uint32_t dmin = __ockl_wfred_min_u32((has && ekey == kmin) ? dkey : 0xffffffffu);
-    const int wl = __builtin_ctzll(__ballot(has && ekey == kmin && dkey == dmin));  // lane 0 has a slot: never empty
-    auto bcast = [&](float v) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), wl)); };
-    const float sb = bcast(take1 ? sv.y : sv.x);
-    const float ob = bcast(take1 ? ov.y : ov.x);
-    const float erb = bcast(eb);
-    if (lane == 0) {
-      out_idx[r] = (int32_t)(dmin >> 1);
-      out_s[r] = sb;
-      out_o[r] = ob;
-      out_sym[r] = (uint8_t)(dmin & 1u);
-      out_err[r] = erb;
-    }
-    return;
-  }
-  const uint32_t smin = __ockl_wfred_min_u32((has && ekey == kmin) ? slot : 0xffffffffu);
-  const int wl = (int)(smin < (uint32_t)K ? smin : smin - (uint32_t)K);
+  uint32_t key = slot;  // FitOrder<FIT>::key of the lane's best, as the u32 the reduction takes
+  if constexpr (FIT == kFitClipped) key = (uint32_t)(ci < 0 ? 0 : ci) * 2u + (take1 ? 1u : 0u);
+  const uint32_t key_min = __ockl_wfred_min_u32((has && ekey == kmin) ? key : 0xffffffffu);
+  int wl;  // the winning lane
+  if constexpr (FIT == kFitClipped)  // several lanes can hold the key: the first (lane 0 has a slot: never empty)
+    wl = __builtin_ctzll(__ballot(has && ekey == kmin && key == key_min));
+  else
+    wl = (int)(key_min < (uint32_t)K ? key_min : key_min - (uint32_t)K);
   auto bcast = [&](float v) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), wl)); };
   const float sb = bcast(take1 ? sv.y : sv.x);
   const float ob = bcast(take1 ? ov.y : ov.x);
   const float erb = bcast(eb);
-  const int db = __builtin_amdgcn_readlane(ci < 0 ? 0 : ci, wl);
+  int db;  // the winner's domain: in the key, or the winning lane's
+  if constexpr (FIT == kFitClipped) db = (int32_t)(key_min >> 1);
+  else db = __builtin_amdgcn_readlane(ci < 0 ? 0 : ci, wl);
   if (lane == 0) {
     out_idx[r] = db;
-    out_s[r] = clip_sym(sb, fabsf(s_clip));
+    out_s[r] = FIT == kFitClipped ? sb : clip_sym(sb, fabsf(s_clip));
     out_o[r] = ob;
-    out_sym[r] = (uint8_t)(smin >= (uint32_t)K);
+    out_sym[r] = (uint8_t)(FIT == kFitClipped ? (key_min & 1u) : (uint32_t)(key_min >= (uint32_t)K));
     out_err[r] = erb;
   }
 }
@@ -362,7 +370,7 @@ __global__ __launch_bounds__(64 * kAffWaves) void k_affine_batch(const float* __
   }
   float D[kAffBatch][RS];
 #pragma unroll
-  for (int j = 0; j < kAffBatch; ++j) gather_row<RS>(pool, c[j], D[j]);
+  for (int j = 0; j < kAffBatch; ++j) gather_row<RS>(pool, c[j] < 0 ? 0 : c[j], D[j]);
 #if FWAV_AFF_ABL
   // ablation build (tools/affine_probe.py): the same loads, no solve — the memory side's time alone
   float acc = 0.0f;
@@ -416,6 +424,8 @@ __device__ __forceinline__ void pair_errors(const float* __restrict__ R, int rs,
     const float rm = pw_sum_n<RS>(fr) / (float)RS;
 #pragma unroll
     for (int i = 0; i < RS; ++i) rc[i] = Rr[i] - rm;
+    // (not gather_row: through it k_tie_check<4, *> comes out with six adds' operands swapped — the same sums, but its
+    // code is kept text-identical to what it was)
 #pragma unroll
     for (int i = 0; i < RS; ++i) D[i] = pool[(int64_t)di * RS + i];
 #pragma unroll
@@ -424,29 +434,11 @@ __device__ __forceinline__ void pair_errors(const float* __restrict__ R, int rs,
     eval_orient<RS>(D, Rr, rc, rm, s0, o0, e0);
     eval_orient<RS>(M, Rr, rc, rm, s1, o1, e1);
   } else {
-    const int n = rs;
     auto fr = [&](int i) { return R[i]; };
-    const float rm = pw_sum(fr, n) / (float)n;
-    const float* D = pool + (int64_t)di * n;
-    float ee[2];
-    for (int orient = 0; orient < 2; ++orient) {
-      auto X = [&](int i) { return orient ? D[n - 1 - i] : D[i]; };
-      const float dm = pw_sum(X, n) / (float)n;
-      auto fn = [&](int i) { return (X(i) - dm) * (R[i] - rm); };
-      auto fd = [&](int i) {
-        const float t = X(i) - dm;
-        return t * t;
-      };
-      const float num = pw_sum(fn, n);
-      const float den = pw_sum(fd, n) + 1e-12f;
-      const float s = num / den;
-      const float o = rm - s * dm;
-      auto fe = [&](int i) {
-        const float df = (s * X(i) + o) - R[i];
-        return df * df;
-      };
-      ee[orient] = sqrtf(pw_sum(fe, n));
-    }
+    const float rm = pw_sum(fr, rs) / (float)rs;
+    const float* D = pool + (int64_t)di * rs;
+    float ee[2], s, o;
+    for (int orient = 0; orient < 2; ++orient) fit_any<kFitReference>(D, orient, R, rm, rs, 0.f, s, o, ee[orient]);
     e0 = ee[0];
     e1 = ee[1];
   }
@@ -490,15 +482,16 @@ __global__ __launch_bounds__(256) void k_tie_check(const float* __restrict__ ran
     pair_errors<RS>(R, rs, pool, di, e0, e1);
     if (ci < 0) { e0 = INFINITY; e1 = INFINITY; }
     // the minimum error (first-minimum / NaN-first order of the reference's argmin)
+    // (its own two-value loop, not wave_best: it reduces under a lane mask and carries no tuple)
     auto arg_min = [&](bool on, float& be, int& bs) {
       be = on ? e0 : INFINITY;
       bs = on ? lane : 0x7fffffff;
-      if (on && better(e1, K + lane, be, bs)) { be = e1; bs = K + lane; }
+      if (on && first_min(e1, K + lane, be, bs)) { be = e1; bs = K + lane; }
 #pragma unroll
       for (int m = 1; m < 64; m <<= 1) {
         const float oe = __shfl_xor(be, m);
         const int os = __shfl_xor(bs, m);
-        if (better(oe, os, be, bs)) { be = oe; bs = os; }
+        if (first_min(oe, os, be, bs)) { be = oe; bs = os; }
       }
     };
     float be;
@@ -606,30 +599,17 @@ static int affine_launch(const char* what, const float* ranges, int64_t nr, int 
   FWAV_CHECK_ARG(rs <= kMaxPairwise, FWAV_ERR_SHAPE, "%s: rs > %d", what, kMaxPairwise);
   if (nr == 0) return FWAV_OK;
   hipStream_t st = (hipStream_t)stream;
-  const int64_t grid = cdiv(nr, kAffWaves);
-  const int thr = 64 * kAffWaves;
-  if (K <= 64 && (rs == 4 || rs == 8 || rs == 16)) {
-    switch (rs) {
-#define FWAV_AFF_PIPE(RSV)                                                                                        \
-  case RSV:                                                                                                       \
-    k_affine_batch<RSV, FIT><<<cdiv(nr, kAffWaves * kAffBatch), thr, 0, st>>>(ranges, nr, cand, K, pool, s_clip,  \
-                                                                              out_idx, out_s, out_o, out_sym,     \
-                                                                              out_err);                           \
-    break;
-      FWAV_AFF_PIPE(4)
-      FWAV_AFF_PIPE(8)
-      FWAV_AFF_PIPE(16)
-#undef FWAV_AFF_PIPE
-    }
-    FWAV_LAUNCH_CHECK(what);
-    return FWAV_OK;
-  }
+  // a kernel whose waves take `per_wave` ranges each; `len`: the run-time length, for the kernel that takes one
+  auto go = [&](auto kern, int per_wave, auto... len) {
+    kern<<<cdiv(nr, kAffWaves * per_wave), 64 * kAffWaves, 0, st>>>(ranges, nr, len..., cand, K, pool, s_clip, out_idx,
+                                                                     out_s, out_o, out_sym, out_err);
+  };
+  auto fixed = [&](auto batch, auto strided) { K <= 64 ? go(batch, kAffBatch) : go(strided, 1); };
   switch (rs) {
-    case 4: k_affine<4, FIT><<<grid, thr, 0, st>>>(ranges, nr, cand, K, pool, s_clip, out_idx, out_s, out_o, out_sym, out_err); break;
-    case 8: k_affine<8, FIT><<<grid, thr, 0, st>>>(ranges, nr, cand, K, pool, s_clip, out_idx, out_s, out_o, out_sym, out_err); break;
-    case 16: k_affine<16, FIT><<<grid, thr, 0, st>>>(ranges, nr, cand, K, pool, s_clip, out_idx, out_s, out_o, out_sym, out_err); break;
-    default:
-      k_affine_any<FIT><<<grid, thr, 0, st>>>(ranges, nr, rs, cand, K, pool, s_clip, out_idx, out_s, out_o, out_sym, out_err);
+    case 4: fixed(k_affine_batch<4, FIT>, k_affine<4, FIT>); break;
+    case 8: fixed(k_affine_batch<8, FIT>, k_affine<8, FIT>); break;
+    case 16: fixed(k_affine_batch<16, FIT>, k_affine<16, FIT>); break;
+    default: go(k_affine_any<FIT>, 1, rs);
   }
   FWAV_LAUNCH_CHECK(what);
   return FWAV_OK;
@@ -660,25 +640,12 @@ static int tie_check_launch(const char* what, const float* ranges, int64_t n_ran
   if (max_ties == 0) return FWAV_OK;
   const SgemvSplit sp = make_sgemv_split_dim(nd, blas_threads, emb_dim);
   const int64_t grid = cdiv(max_ties, 4);
-#define FWAV_TIE(RSV, EDV)                                                                                         \
-  k_tie_check<RSV, EDV><<<grid, 256, 0, st>>>(ranges, rs, cand, K, pool, emb, q_offset, sp, ties, exact_sets, resolve, \
-                                              qemb)
-  if (emb_dim == 32) {
-    switch (rs) {
-      case 4: FWAV_TIE(4, 32); break;
-      case 8: FWAV_TIE(8, 32); break;
-      case 16: FWAV_TIE(16, 32); break;
-      default: FWAV_TIE(0, 32);
-    }
-  } else {
-    switch (rs) {
-      case 4: FWAV_TIE(4, 16); break;
-      case 8: FWAV_TIE(8, 16); break;
-      case 16: FWAV_TIE(16, 16); break;
-      default: FWAV_TIE(0, 16);
-    }
-  }
-#undef FWAV_TIE
+  // [embedding width 32, 16][rs 4, 8, 16, any other]
+  static constexpr decltype(&k_tie_check<0, 16>) kern[2][4] = {
+      {k_tie_check<4, 32>, k_tie_check<8, 32>, k_tie_check<16, 32>, k_tie_check<0, 32>},
+      {k_tie_check<4, 16>, k_tie_check<8, 16>, k_tie_check<16, 16>, k_tie_check<0, 16>}};
+  kern[emb_dim == 32 ? 0 : 1][rs == 4 ? 0 : rs == 8 ? 1 : rs == 16 ? 2 : 3]<<<grid, 256, 0, st>>>(
+      ranges, rs, cand, K, pool, emb, q_offset, sp, ties, exact_sets, resolve, qemb);
   FWAV_LAUNCH_CHECK(what);
   return FWAV_OK;
 }
