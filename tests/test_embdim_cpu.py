@@ -7,10 +7,10 @@ import numpy as np
 import pytest
 
 from oracle import fractal_oracle as O
+from split_edges import THREAD_MIN_MN, col_kinds, sgemv_dim_np, unit_head_rows  # noqa: F401
 
 F32 = np.float32
 D = 32
-THREAD_MIN_MN = 460800  # OpenBLAS: sgemv on one thread while m·n is below this
 
 
 @pytest.fixture(scope="module")
@@ -22,44 +22,6 @@ def lib():
 
 
 # ------------------------------------------------------------------------------------------------ sgemv order
-def col_kinds(nd: int, threads: int, dim: int = D) -> np.ndarray:
-    """fwav_common.h make_sgemv_split_dim + sgemv_kind: which sgemv_t kernel scores each of the nd columns."""
-    T = 1 if dim * nd < THREAD_MIN_MN else max(1, int(threads))
-    q, r = divmod(nd, T)
-    d = np.arange(nd)
-    big = d < r * (q + 1)
-    w = np.where(big, q + 1, q)
-    start = np.where(big, d // (q + 1) * (q + 1), r * (q + 1) + (d - r * (q + 1)) // max(q, 1) * q)
-    pos, t = d - start, w & 3
-    return np.where(pos < w - t, 0, np.where(((t & 2) != 0) & (pos < w - t + 2), 1, 2)), {int(x) for x in np.unique(w)}
-
-
-def sgemv_dim_np(E: np.ndarray, q: np.ndarray, kinds: np.ndarray) -> np.ndarray:
-    """fwav_common.h sgemv_dim on every row of E (nd, dim), restated in numpy."""
-    E, q = np.asarray(E, F32), np.asarray(q, F32)
-    nd, dim = E.shape
-    P = E * q[None, :]  # separately rounded f32 products
-    l0 = np.zeros((nd, 8), F32)
-    for b in range(dim // 8):
-        sl = slice(8 * b, 8 * b + 8)
-        l0 = O.fma_f32(E[:, sl].astype(np.float64) * q[None, sl].astype(np.float64), l0.astype(np.float64))
-    fold8 = lambda l: ((l[:, 0] + l[:, 4]) + (l[:, 1] + l[:, 5])) + ((l[:, 2] + l[:, 6]) + (l[:, 3] + l[:, 7]))  # noqa: E731
-    l1 = np.zeros((nd, 4), F32)
-    l2 = np.zeros((nd, 8), F32)
-    for k in range(dim):
-        l1[:, k % 4] = l1[:, k % 4] + P[:, k]
-        l2[:, k % 8] = l2[:, k % 8] + P[:, k]
-    k1 = (l1[:, 0] + l1[:, 1]) + (l1[:, 2] + l1[:, 3])
-    return np.where(kinds == 0, fold8(l0), np.where(kinds == 1, k1, fold8(l2))).astype(F32)
-
-
-def unit_head_rows(rng, n: int, dim: int = D) -> np.ndarray:
-    """n rows of two f32 heads, each normalised in f32 as the reference normalises them."""
-    x = rng.normal(0, 1, (n, 2, dim // 2)).astype(F32)
-    x = x / np.sqrt((x * x).sum(-1, dtype=F32))[..., None]
-    return np.ascontiguousarray(x.reshape(n, dim).astype(F32))
-
-
 def test_sgemv_order_pinned_against_numpy():
     """The restatement of sgemv_dim and of the thread split equals numpy's ``A @ q`` bit for bit at D = 32: one thread
     and this host's count, nd on both sides of D·nd = 460,800, chunk widths of every residue mod 4."""
