@@ -292,16 +292,9 @@ __global__ void k_energy_chain(const float* __restrict__ bufsum, int64_t nb, flo
 //                       0..min(K,nd)−1
 //   otherwise         → appended to `active` for the similarity search
 // RS > 0: compile-time range size (row in registers, unrolled pairwise sum); RS == 0: runtime rs.
-template <int RS, int ED = 16>
-__global__ void k_prune(const float* __restrict__ ranges, int64_t nr, int64_t q_offset, int rs_rt, float thr,
-                        int fast_mode, const float* __restrict__ emb, int64_t nd, int k,
-                        const int32_t* __restrict__ zero_cand, int32_t* __restrict__ cand,
-                        int32_t* __restrict__ active, int32_t* __restrict__ n_active) {
-  // (emb: the table the query rows are read from — the domain table, quirk Q1, or fwav_prune_q's query table)
-  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= nr) return;
-  const int rs = RS > 0 ? RS : rs_rt;
-  const float* r = ranges + i * rs;
+// The energy prune's predicate (fractal.py:601-603): mean(r²) < thr, in fast_mode only.
+template <int RS>
+__device__ __forceinline__ bool energy_pruned(const float* __restrict__ r, int rs, float thr, int fast_mode) {
   float mean_sq;
   if constexpr (RS > 0) {
     float v[RS];
@@ -321,7 +314,33 @@ __global__ void k_prune(const float* __restrict__ ranges, int64_t nr, int64_t q_
     auto sq = [&](int j) { return r[j] * r[j]; };
     mean_sq = pw_sum(sq, rs) / (float)rs;
   }
-  bool pruned = fast_mode && (mean_sq < thr);
+  return fast_mode && (mean_sq < thr);
+}
+
+// Appends the ranges of this wave for which `act` holds to `active`: one counter atomic per wave (not per range),
+// index order kept within a wave.
+__device__ __forceinline__ void append_active(bool act, int64_t i, int32_t* __restrict__ active,
+                                              int32_t* __restrict__ n_active) {
+  const uint64_t m = __ballot(act);
+  if (m == 0ull) return;
+  const int lane = threadIdx.x & 63;
+  const int leader = __builtin_ctzll(m);
+  int base = 0;
+  if (lane == leader) base = atomicAdd(n_active, __popcll(m));
+  base = __shfl(base, leader);
+  if (act) active[base + __popcll(m & ((1ull << lane) - 1ull))] = (int32_t)i;
+}
+
+template <int RS, int ED = 16>
+__global__ void k_prune(const float* __restrict__ ranges, int64_t nr, int64_t q_offset, int rs_rt, float thr,
+                        int fast_mode, const float* __restrict__ emb, int64_t nd, int k,
+                        const int32_t* __restrict__ zero_cand, int32_t* __restrict__ cand,
+                        int32_t* __restrict__ active, int32_t* __restrict__ n_active) {
+  // (emb: the table the query rows are read from — the domain table, quirk Q1, or fwav_prune_q's query table)
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nr) return;
+  const int rs = RS > 0 ? RS : rs_rt;
+  const bool pruned = energy_pruned<RS>(ranges + i * rs, rs, thr, fast_mode);
   bool zero = true;
   if (!pruned) {
     const float4* q = reinterpret_cast<const float4*>(emb + (i + q_offset) * ED);
@@ -341,16 +360,17 @@ __global__ void k_prune(const float* __restrict__ ranges, int64_t nr, int64_t q_
       for (int j = 0; j < k; ++j) c[j] = j < nd ? j : -1;
     }
   }
-  // append the searchable ranges: one counter atomic per wave (not per range), index order kept within a wave
-  const bool act = !pruned && !zero;
-  const uint64_t m = __ballot(act);
-  if (m == 0ull) return;
-  const int lane = threadIdx.x & 63;
-  const int leader = __builtin_ctzll(m);
-  int base = 0;
-  if (lane == leader) base = atomicAdd(n_active, __popcll(m));
-  base = __shfl(base, leader);
-  if (act) active[base + __popcll(m & ((1ull << lane) - 1ull))] = (int32_t)i;
+  append_active(!pruned && !zero, i, active, n_active);  // the searchable ranges
+}
+
+// The energy prune alone (fwav_prune_energy): the ranges k_prune's predicate keeps, appended to `active`.
+template <int RS>
+__global__ void k_prune_energy(const float* __restrict__ ranges, int64_t nr, int rs_rt, float thr, int fast_mode,
+                               int32_t* __restrict__ active, int32_t* __restrict__ n_active) {
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nr) return;
+  const int rs = RS > 0 ? RS : rs_rt;
+  append_active(!energy_pruned<RS>(ranges + i * rs, rs, thr, fast_mode), i, active, n_active);
 }
 
 }  // namespace fwav
@@ -493,6 +513,26 @@ int fwav_prune_dim(const float* ranges, int64_t nr, int64_t q_offset, int rs, fl
   FWAV_CHECK_ARG(emb_dim == 32, FWAV_ERR_ARG, "fwav_prune_dim: emb_dim %d (only 32 is supported)", emb_dim);
   return prune_launch("fwav_prune_dim", ranges, nr, q_offset, rs, prune_thr, fast_mode, emb, nd, nd, emb_dim, k,
                       zero_cand, cand, active, n_active, stream);
+}
+
+// The energy prune without a query: local range i of [0, nr) is appended to active[] (*n_active) unless fast_mode and
+// mean(r²) < prune_thr — fwav_prune's first rule by the same code, and no other (fwav_affine_all's list).
+int fwav_prune_energy(const float* ranges, int64_t nr, int rs, float prune_thr, int fast_mode, int32_t* active,
+                      int32_t* n_active, void* stream) {
+  FWAV_CHECK_ARG(ranges && active && n_active, FWAV_ERR_ARG, "fwav_prune_energy: null pointer");
+  FWAV_CHECK_ARG(nr >= 0 && rs >= 1 && rs <= kMaxPairwise, FWAV_ERR_SHAPE, "fwav_prune_energy: bad shape");
+  hipStream_t st = (hipStream_t)stream;
+  (void)hipMemsetAsync(n_active, 0, sizeof(int32_t), st);
+  if (nr == 0) return FWAV_OK;
+  const int64_t grid = cdiv(nr, kSignalThreads);
+  switch (rs) {
+    case 4: k_prune_energy<4><<<grid, kSignalThreads, 0, st>>>(ranges, nr, rs, prune_thr, fast_mode, active, n_active); break;
+    case 8: k_prune_energy<8><<<grid, kSignalThreads, 0, st>>>(ranges, nr, rs, prune_thr, fast_mode, active, n_active); break;
+    case 16: k_prune_energy<16><<<grid, kSignalThreads, 0, st>>>(ranges, nr, rs, prune_thr, fast_mode, active, n_active); break;
+    default: k_prune_energy<0><<<grid, kSignalThreads, 0, st>>>(ranges, nr, rs, prune_thr, fast_mode, active, n_active);
+  }
+  FWAV_LAUNCH_CHECK("fwav_prune_energy");
+  return FWAV_OK;
 }
 
 }  // extern "C"

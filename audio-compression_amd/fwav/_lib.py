@@ -52,6 +52,11 @@ SIGNATURES = {
     "fwav_debug_gather_rows": (I32, [P, I64, I32, I64, P, P]),
     "fwav_affine": (I32, [P, I64, I32, P, I32, P, I64, F32, P, P, P, P, P, P]),
     "fwav_affine_fit": (I32, [P, I64, I32, P, I32, P, I64, F32, P, P, P, P, P, I32, P]),
+    "fwav_affine_all_workspace_size": (SZ, [I64, I64, I32]),
+    "fwav_affine_all_tile_rows": (I32, [I32]),
+    "fwav_affine_all_slices": (I32, [I64, I64, I32]),
+    "fwav_affine_all": (I32, [P, I64, I32, P, P, I64, P, I64, F32, P, P, P, P, P, I32, P, SZ, P]),
+    "fwav_prune_energy": (I32, [P, I64, I32, F32, I32, P, P, P]),
     "fwav_tie_check": (I32, [P, I64, I32, P, I32, P, I64, P, I64, I32, P, I64, I32, P, P]),
     "fwav_tie_rows_in": (I32, [P, I64, P, I32, P, P, I32, P, P]),
     "fwav_tie_rows_out": (I32, [P, I64, P, P, P, P, P, P, P, P, P, P, P]),

@@ -46,7 +46,7 @@ def _default_k():
 def compress_audio(signal, framerate, sampwidth, tile_size=1024, emb_dim=16, top_k=None, ef_search=50, use_gpu=False,
                    energy_thresh=1e-4, domains_tmpdir=None, batch_size_gpu=512, batch_size_cpu=128, fast_mode=True,
                    transient_weight=1.0, n_mels=40, cpu_workers=None, batch_size=None, device=None,
-                   embedding="matrix", compact=False, query="domain_row", fit="reference"):
+                   embedding="matrix", compact=False, query="domain_row", fit="reference", candidates="embedding"):
     """fractal.py:1045 — returns ``(matches, domains, n_ranges, range_size, tile_size, domain_step,
     energy_thresh, original_len)``.  ``embedding`` as :func:`fwav.engine.compress_device`: "pocketfft" embeds with
     scipy's own DCT sequence at every supported range size (ValueError at the others), so that tiles of 4352 samples
@@ -61,22 +61,30 @@ def compress_audio(signal, framerate, sampwidth, tile_size=1024, emb_dim=16, top
     ``fit="clipped"`` (opt-in; :func:`fwav.engine.compress_device`) picks, among the same candidates, the slot whose
     stored tuple — s clipped to ±16 before o and err are computed — fits best, instead of the slot whose unclipped s
     does: ``err`` is then the error of what the file holds, and the decoder (s_damping > 0) reproduces it (README
-    §fit).  The same return tuple and file format; not the reference's matches."""
+    §fit).  The same return tuple and file format; not the reference's matches.
+    ``candidates="all"`` (opt-in; :func:`fwav.engine.compress_device`) picks each match among every domain of the pool
+    instead of the ``top_k`` the embedding search proposes: the best-fitting file the format allows and the ceiling
+    that ``top_k``, ``query`` and ``emb_dim`` approach (all three are then validated and unused), at a cost that grows
+    as n_ranges · n_domains (README §candidates).  The same return tuple, file format and decoder; works with
+    ``compact=True``."""
     engine.check_emb_dim(emb_dim, embedding)  # 16 or 32; NotImplementedError for any other width
     k = _default_k() if top_k is None else int(top_k)
     engine.check_query(query, emb_dim, k)  # before any device work
     engine.check_fit(fit)
+    engine.check_candidates(candidates)
     dev = engine.require_device(device)
     sig = np.asarray(signal, dtype=np.float32)
     rs, step = engine.geometry(tile_size)
     t = torch.from_numpy(np.ascontiguousarray(sig)).to(dev)
     if compact:  # the full pool never leaves the device: no side-stream copy of it
         res = engine.compress_device(t, tile_size, k, energy_thresh=energy_thresh, fast_mode=fast_mode,
-                                     embedding=embedding, emb_dim=emb_dim, query=query, fit=fit)
+                                     embedding=embedding, emb_dim=emb_dim, query=query, fit=fit,
+                                     candidates=candidates)
         return device_result_to_tuple(engine.compact_device(res), pinned_pool=True)
     copy = _PoolCopy(dev)
     res = engine.compress_device(t, tile_size, k, energy_thresh=energy_thresh, fast_mode=fast_mode,
-                                 on_pool=copy.start, embedding=embedding, emb_dim=emb_dim, query=query, fit=fit)
+                                 on_pool=copy.start, embedding=embedding, emb_dim=emb_dim, query=query, fit=fit,
+                                 candidates=candidates)
     return device_result_to_tuple(res, copy)
 
 
@@ -198,9 +206,9 @@ def compute_snr(original, reconstructed):
 
 
 def process_file_compress(path, outdir=None, tile=1024, energy_thresh=1e-4, use_gpu=False, embedding="matrix",
-                          emb_dim=16, compact=False, query="domain_row", fit="reference"):
+                          emb_dim=16, compact=False, query="domain_row", fit="reference", candidates="embedding"):
     """fractal.py:1491-1521 (the positional CLI OUTPUT is used as a directory, quirk Q8).  ``embedding``,
-    ``emb_dim``, ``compact``, ``query`` and ``fit`` as :func:`compress_audio`."""
+    ``emb_dim``, ``compact``, ``query``, ``fit`` and ``candidates`` as :func:`compress_audio`."""
     try:
         start = time.time()
         signal, framerate, sampwidth = read_wav_mono(path)
@@ -208,7 +216,8 @@ def process_file_compress(path, outdir=None, tile=1024, energy_thresh=1e-4, use_
             signal = np.clip(signal.astype(np.float32), -1.0, 1.0)
         matches, domains, n_ranges, range_size, tile_size, domain_step, energy_threshold, original_len = \
             compress_audio(signal, framerate, sampwidth, tile_size=tile, energy_thresh=energy_thresh, use_gpu=use_gpu,
-                           embedding=embedding, emb_dim=emb_dim, compact=compact, query=query, fit=fit)
+                           embedding=embedding, emb_dim=emb_dim, compact=compact, query=query, fit=fit,
+                           candidates=candidates)
         logger.info(f"Processed {len(matches)} ranges, domain matrix shape {domains.shape}")
         if outdir and not os.path.exists(outdir):
             os.makedirs(outdir)

@@ -3,11 +3,14 @@
   python fractal.py compress IN OUT [--tile 1024] [--energy-thresh 1e-4] [--gpu] [--batch] [--out DIR] [--workers 4]
                             [--embedding {matrix,pocketfft}] [--emb-dim {16,32}]
                             [--compact] [--query {domain_row,range}] [--fit {reference,clipped}]
+                            [--candidates {embedding,all}]
   python fractal.py decompress IN [--out PATH] [--iter 8] [--eps 1e-3] [--gpu] [--batch] [--workers 4]
                               [--s-damping 0.0]
   python fractal.py compact IN.fwav [--out PATH]
 
---embedding, --emb-dim, --compact, --query, --fit, --s-damping and the compact sub-command are this port's extras.  --fit
+--embedding, --emb-dim, --compact, --query, --fit, --candidates, --s-damping and the compact sub-command are this port's
+extras.  --candidates all picks each match among every domain of the pool instead of the 32 the embedding search
+proposes: the best-fitting file the format allows, at a cost that grows as ranges × domains.  --fit
 clipped stores, among the same candidates, the match whose stored tuple (s clipped to ±16 first) fits best, and the
 error of that tuple; the default is the reference's selection by the unclipped scale.  --query
 range searches with each range's own embedding instead of the reference pipeline's domain row i (quirk Q1): better
@@ -107,6 +110,9 @@ def build_parser() -> argparse.ArgumentParser:
     pc.add_argument("--fit", choices=("reference", "clipped"), default="reference",
                     help="match selection: by the error of the unclipped scale, as the reference (s is clipped "
                          "afterwards), or by the error of the tuple that is stored (not the reference's file)")
+    pc.add_argument("--candidates", choices=("embedding", "all"), default="embedding",
+                    help="the domains a match is picked among: those the embedding search proposes, or every domain "
+                         "of the pool (the best match there is; time grows as ranges x domains)")
     pk = sub.add_parser("compact")
     pk.add_argument("input", help="input FWAV file")
     pk.add_argument("--out", default=None, help="output FWAV file (default: IN with .compact.fwav for .fwav)")
@@ -134,7 +140,7 @@ def main(argv=None):
             if args.output is None:
                 parser.error("compress requires OUTPUT unless --batch is used")
             return _compress_job((args.input, args.output, args.tile, args.energy_thresh, args.gpu, args.embedding,
-                                  args.emb_dim, args.compact, args.query, args.fit))
+                                  args.emb_dim, args.compact, args.query, args.fit, args.candidates))
         if args.output is not None:
             parser.error("Do not provide positional OUTPUT when using --batch; use --out instead")
         out_dir = args.out or args.input
@@ -146,7 +152,7 @@ def main(argv=None):
             return None
         results = _run_pool(_compress_job, [(f, os.path.join(out_dir, os.path.basename(f) + ".fwav"), args.tile,
                                              args.energy_thresh, args.gpu, args.embedding, args.emb_dim, args.compact,
-                                             args.query, args.fit)
+                                             args.query, args.fit, args.candidates)
                                             for f in todo],
                             args.workers)
         metrics_file = os.path.join(out_dir, "compression_metrics.json")

@@ -15,6 +15,8 @@ Reference map (``/root/reference/fractal.py``):
   the same stages on rows of emb_dim = 32 columns (:275)   → fwav_pool_embed_dim, fwav_prune_dim, fwav_sim_topk_dim, …
   _process_gpu_batch :757-850                              → fwav_affine
   (no counterpart; opt-in) the same solve selecting by the stored tuple's error → fwav_affine_fit (fit="clipped")
+  (no counterpart; opt-in) the same solve over every domain of the pool → fwav_prune_energy + fwav_affine_all
+                                                             (candidates="all")
   decompress_audio :1378-1473                              → fwav_decode
   (no counterpart; opt-in) the pool rows that :1414 reads   → fwav_compact_domains (compact_device / compact_arrays)
   (no counterpart call; opt-in) range_candidates_from_embedding :337-351, each range's own embedding as its query
@@ -30,8 +32,8 @@ import torch
 from . import _lib, geometry, stages, ties as _ties  # noqa: F401  geometry: re-exported
 from .nporder import zero_query_candidates  # noqa: F401  (Q11 rows; re-exported)
 from ._lib import FwavError, call, size_call
-from .stages import (EMB_DIMS, EMBEDDINGS, FITS, QUERIES, QUERY_RANGE_MAX_K, TIE_MODES, TIE_REC,  # noqa: F401  re-exported
-                     check_emb_dim, check_embedding, check_fit, check_query, n_domains_for)
+from .stages import (CANDIDATES, EMB_DIMS, EMBEDDINGS, FITS, QUERIES, QUERY_RANGE_MAX_K, TIE_MODES, TIE_REC,  # noqa: F401  re-exported
+                     check_candidates, check_emb_dim, check_embedding, check_fit, check_query, n_domains_for)
 
 
 def require_device(device=None) -> torch.device:
@@ -183,7 +185,8 @@ def _compress_device(sig: torch.Tensor, tile_size: int, top_k: int, energy_thres
                      search: str = "f16", on_pool=None, blas_threads: Optional[int] = None,
                      tie_order: str = "numpy", defer_ties: bool = False,
                      sub_blocks: Optional[int] = None, embedding: str = "matrix",
-                     emb_dim: int = 16, query: str = "domain_row", fit: str = "reference") -> DeviceCompressed:
+                     emb_dim: int = 16, query: str = "domain_row", fit: str = "reference",
+                     candidates: str = "embedding") -> DeviceCompressed:
     """Run the compress hot path on ``sig`` (1-D float32 tensor on a HIP device).
 
     ``shard=(lo, hi)`` restricts candidate search and the affine solve to ranges ``[lo, hi)`` (the
@@ -228,6 +231,16 @@ def _compress_device(sig: torch.Tensor, tile_size: int, top_k: int, energy_thres
     after the search, so it composes with every option above; the whole call — sub-blocks, a shard, the re-solve of
     host-ranked tie rows, deferred or not — solves in the one mode.  The tie check tests the reference's error, so
     ``tie_order="numpy"`` then ranks every K-th place tie on the host, as "numpy_sets" does (stages.tie_mode).
+    ``candidates="all"`` (opt-in; the default "embedding" is everything above) picks each range's match among every
+    domain of the pool instead of the K that the embedding search proposes (fwav_affine_all): the tuple is what the
+    affine solve gives for the candidate row 0 … n_domains − 1 in the call's ``fit``, so it is the best match the pool
+    holds — the ceiling that ``top_k``, ``query`` and ``emb_dim`` approach.  The searched ranges are those the energy
+    prune keeps (every range without ``fast_mode``); a pruned range gets the tuple the default path gives a pruned
+    range (the solve of an all-−1 candidate row).  No query table, zero-query rule, search, tie list or tie check runs,
+    so ``top_k``, ``query``, ``emb_dim``, ``embedding``, ``tie_order`` and ``search`` are validated and then unused,
+    ``res.cand`` is None and ``n_ties`` = ``n_resolved`` = 0; there is no Q9 error (no query indexes the domain table).
+    ``shard``, ``s_clip``, ``fit``, ``on_pool`` and ``events`` (mark "affine_all") work as above.  The cost is
+    n_searched · n_domains fits: a second at cfg2 where the default search takes milliseconds.
     """
     if sig.dim() != 1 or sig.dtype != torch.float32 or not sig.is_cuda:
         raise ValueError("compress_device expects a 1-D float32 device tensor")
@@ -248,6 +261,7 @@ def _compress_device(sig: torch.Tensor, tile_size: int, top_k: int, energy_thres
     check_query(query, dim, k)
     stages.check_tie_order(tie_order)
     check_fit(fit)
+    all_domains = stages.check_candidates(candidates) == "all"
     threads = _ties.blas_threads() if blas_threads is None else int(blas_threads)
     _mark(events, "voiced_ranges")
     ranges = _voiced_ranges(sig, n, rs, energy_thresh, st)
@@ -258,18 +272,20 @@ def _compress_device(sig: torch.Tensor, tile_size: int, top_k: int, energy_thres
     _mark(events, "voiced_ranges")
     res = DeviceCompressed(nr, rs, tile_size, step, energy_thresh, n, nd, k, (0, nr), energy_partial=partial,
                            stream=torch.cuda.current_stream(dev))
-    if n < tile_size or (nr > nd and query != "range"):
+    if n < tile_size or (nr > nd and query != "range" and not all_domains):
         # the reference returns the empty tuple for silent input before it ever builds domains
         if res.is_silent() or n < tile_size:
             return _empty(n, rs, tile_size, step, energy_thresh, k)
         raise ValueError("mmap length is greater than file size")  # quirk Q9 (fractal.py:1190-1195)
-    tab = embed_tables(rs, dev, embedding, dim)
-    pool = torch.empty(nd * rs, dtype=torch.float32, device=dev)
-    emb = torch.empty(nd * dim, dtype=torch.float32, device=dev)
     if search not in ("f16", "f32"):
         raise ValueError("search must be 'f16' (fp16 pre-filter + exact f32 rescoring) or 'f32'")
     if dim != 16 and search != "f16":
         raise ValueError("search='f32' is not available with emb_dim=32 (the wide search has one kernel)")
+    if all_domains:  # the embedding is not used: the pool stage in its plainest form (there is no pool-only call)
+        embedding, dim, search = "matrix", 16, "f32"
+    tab = embed_tables(rs, dev, embedding, dim)
+    pool = torch.empty(nd * rs, dtype=torch.float32, device=dev)
+    emb = torch.empty(nd * dim, dtype=torch.float32, device=dev)
     emb16 = (torch.empty(stages.emb16_elems(nd, dim), dtype=torch.float16, device=dev) if search == "f16" else None)
     ws_p = size_call("fwav_pool_workspace_size", n, tile_size, rs, step)
     wsp = torch.empty(max(ws_p, 16), dtype=torch.uint8, device=dev)
@@ -279,6 +295,9 @@ def _compress_device(sig: torch.Tensor, tile_size: int, top_k: int, energy_thres
     _mark(events, "pool_embed")
     if on_pool is not None:
         on_pool(pool)
+    if all_domains:
+        return _solve_all_domains(res, ranges, pool, shard, energy_thresh, fast_mode, stages.clip32(s_clip), fit, events,
+                                  keep_intermediates, st)
     qemb = xq = None
     if query == "range":
         # every range's own embedding, by the pool rows' kernel (the whole signal's: a shard's queries are rows lo … hi)
@@ -294,9 +313,7 @@ def _compress_device(sig: torch.Tensor, tile_size: int, top_k: int, energy_thres
     # embedding kernels are queued, so its host synchronisation overlaps them
     if callable(shard):
         shard = shard(ranges, nr, rs)
-    lo, hi = (0, nr) if shard is None else (int(shard[0]), int(shard[1]))
-    if not (0 <= lo <= hi <= nr):
-        raise ValueError(f"bad shard {shard} for {nr} ranges")
+    lo, hi = _shard_bounds(shard, nr)
     res.shard = (lo, hi)
     m = hi - lo
     cand = torch.empty(max(m, 1) * k, dtype=torch.int32, device=dev)
@@ -386,6 +403,51 @@ def _compress_device(sig: torch.Tensor, tile_size: int, top_k: int, energy_thres
             res.ties = ties
         if m > 0 and not sliced:
             res.search_ws = wsk
+    return res
+
+
+def _shard_bounds(shard, nr: int) -> tuple[int, int]:
+    lo, hi = (0, nr) if shard is None else (int(shard[0]), int(shard[1]))
+    if not (0 <= lo <= hi <= nr):
+        raise ValueError(f"bad shard {shard} for {nr} ranges")
+    return lo, hi
+
+
+def _solve_all_domains(res: DeviceCompressed, ranges, pool, shard, energy_thresh, fast_mode, s_clip, fit, events,
+                       keep_intermediates, st) -> DeviceCompressed:
+    """candidates="all": the matches of ranges [lo, hi) among every domain of ``pool``, three launches on the stream
+    ``st``: the solve of an all-−1 row for every range (the tuple of a pruned one), the energy prune's list, and
+    fwav_affine_all over the listed ranges.  Fills and returns ``res``."""
+    dev, nr, rs, nd = ranges.device, res.n_ranges, res.range_size, res.n_domains
+    if callable(shard):
+        shard = shard(ranges, nr, rs)
+    lo, hi = _shard_bounds(shard, nr)
+    res.shard = (lo, hi)
+    m = hi - lo
+    rsh = ranges[lo * rs:hi * rs]
+    active = torch.empty(max(m, 1), dtype=torch.int32, device=dev)
+    n_active = torch.zeros(1, dtype=torch.int32, device=dev)
+    outs = (torch.empty(m, dtype=torch.int32, device=dev), torch.empty(m, dtype=torch.float32, device=dev),
+            torch.empty(m, dtype=torch.float32, device=dev), torch.empty(m, dtype=torch.uint8, device=dev),
+            torch.empty(m, dtype=torch.float32, device=dev))
+    if m > 0:
+        ptrs = [t.data_ptr() for t in outs]
+        _mark(events, "prune")
+        none = torch.full((m,), -1, dtype=torch.int32, device=dev)
+        stages.affine(rsh.data_ptr(), m, rs, none.data_ptr(), 1, pool.data_ptr(), nd, s_clip, ptrs, st, fit=fit)
+        stages.prune_energy(rsh.data_ptr(), m, rs, stages.prune_thr(energy_thresh), int(bool(fast_mode)),
+                            active.data_ptr(), n_active.data_ptr(), st)
+        _mark(events, "prune")
+        wn = stages.affine_all_workspace_size(m, nd, rs)
+        ws = torch.empty(max(wn, 16), dtype=torch.uint8, device=dev)
+        _mark(events, "affine_all")
+        stages.affine_all(rsh.data_ptr(), m, rs, active.data_ptr(), n_active.data_ptr(), m, pool.data_ptr(), nd, s_clip,
+                          ptrs, ws.data_ptr(), wn, st, fit=fit)
+        _mark(events, "affine_all")
+    res.pool, res.n_active = pool, n_active
+    res.idx, res.s, res.o, res.sym, res.err = outs
+    if keep_intermediates:
+        res.ranges, res.active = ranges, active
     return res
 
 

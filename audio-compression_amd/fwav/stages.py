@@ -38,6 +38,9 @@ TIE_REC = 9  # int32 per tie record (kTieRec, fwav_common.h)
 #: scale and clips the stored one afterwards (fractal.py:804-824); "clipped" clips first, so that the error it selects
 #: by and stores is the stored tuple's, and breaks ties by (domain, orientation) instead of the slot
 FITS = ("reference", "clipped")
+#: candidates → the domains the affine solve picks among: the K that the embedding search proposes (the reference's
+#: pipeline), or every domain of the pool (fwav_affine_all: the best match the pool holds; no embedding, no search)
+CANDIDATES = ("embedding", "all")
 
 
 def check_embedding(embedding: str, rs: int) -> str:
@@ -88,6 +91,13 @@ def check_fit(fit: str) -> str:
     if fit not in FITS:
         raise ValueError(f"fit must be 'reference' or 'clipped', not {fit!r}")
     return fit
+
+
+def check_candidates(candidates: str) -> str:
+    """``candidates`` validated (no device work): ValueError for a name other than "embedding" and "all"."""
+    if candidates not in CANDIDATES:
+        raise ValueError(f"candidates must be 'embedding' or 'all', not {candidates!r}")
+    return candidates
 
 
 def tie_mode(tie_order: str, fit: str = "reference") -> int:
@@ -252,6 +262,24 @@ def affine(ranges, n, rs, cand, k, pool, nd, s_clip, outs5, stream, *, fit="refe
         call("fwav_affine", ranges, n, rs, cand, k, pool, nd, s_clip, *outs5, stream)
     else:
         call("fwav_affine_fit", ranges, n, rs, cand, k, pool, nd, s_clip, *outs5, FITS.index(check_fit(fit)), stream)
+
+
+def prune_energy(ranges, n, rs, thr, fast_mode, active, n_active, stream):
+    """The energy prune alone (fwav_prune's first rule, by its code): the kept local ranges into ``active``."""
+    call("fwav_prune_energy", ranges, n, rs, thr, fast_mode, active, n_active, stream)
+
+
+def affine_all_workspace_size(mq: int, nd: int, rs: int) -> int:
+    """Bytes of fwav_affine_all's workspace for a list of at most mq ranges (0 when the domain axis is not split)."""
+    return size_call("fwav_affine_all_workspace_size", mq, nd, rs)
+
+
+def affine_all(ranges, n, rs, active, n_active, max_q, pool, nd, s_clip, outs5, ws, ws_bytes, stream, *,
+               fit="reference"):
+    """The affine solve of the listed ranges over every domain of the pool into ``outs5`` = (idx, s, o, sym, err):
+    fwav_affine_fit's result for the candidate row 0 … nd − 1; ``active`` None lists every range."""
+    call("fwav_affine_all", ranges, n, rs, active, n_active, max_q, pool, nd, s_clip, *outs5,
+         FITS.index(check_fit(fit)), ws, ws_bytes, stream)
 
 
 def tie_fixup(rows, n, new_cand, k, cand, ranges, rs, rsub, tmp5, outs5, pool, nd, s_clip, stream, *, fit="reference"):

@@ -167,6 +167,33 @@ int fwav_affine(const float* ranges, int64_t n_ranges, int range_size, const int
 int fwav_affine_fit(const float* ranges, int64_t n_ranges, int range_size, const int32_t* cand, int k,
                     const float* pool, int64_t n_domains, float s_clip, int32_t* out_idx, float* out_s, float* out_o,
                     uint8_t* out_sym, float* out_err, int fit, void* stream);
+/* ------------------------------------------------------------------- exhaustive affine solve
+ * compress_audio(candidates="all"); no counterpart in the reference, opt-in, and fwav_abi_version is unchanged
+ * (additions only).  For every local range i listed in active[0 .. *n_active) (device; at most max_q entries, each in
+ * [0, n_ranges)) the five outputs are, bit for bit, what fwav_affine_fit writes for the candidate row 0, 1, …,
+ * n_domains − 1 with K = n_domains in the same `fit`: fit 1 clips the slot's s first, computes o and err from that s and
+ * takes the first NaN error, else the smallest, then the smaller domain, then unmirrored; fit 0 takes the reference's
+ * unclipped error, first minimum over [all domains | all mirrored], and clips the stored s afterwards.  Rows that are
+ * not listed are not written.  active == NULL lists every row (n_active is then not read; max_q ≥ n_ranges).  No host
+ * synchronisation and no allocation: when the listed ranges cannot fill the device the domain axis is split over
+ * fwav_affine_all_slices(max_q, n_domains, range_size) workgroup columns whose partial results pass through
+ * `workspace` (device, ≥ fwav_affine_all_workspace_size bytes; 0 with one slice, NULL is then allowed) — the result
+ * does not depend on the split.  fwav_affine_all_tile_rows: the pool rows per on-chip tile at this range size (the
+ * sizes at which the kernel's paths change are its multiples).  A fit outside {0, 1}: FWAV_ERR_ARG before the pointer
+ * checks, as fwav_affine_fit; n_domains < 1 or ≥ 2^30: FWAV_ERR_SHAPE; a short workspace: FWAV_ERR_WORKSPACE.  Work:
+ * n_listed · n_domains · 2 fits. */
+size_t fwav_affine_all_workspace_size(int64_t max_q, int64_t n_domains, int range_size);
+int fwav_affine_all_tile_rows(int range_size);
+int fwav_affine_all_slices(int64_t max_q, int64_t n_domains, int range_size);
+int fwav_affine_all(const float* ranges, int64_t n_ranges, int range_size, const int32_t* active,
+                    const int32_t* n_active, int64_t max_q, const float* pool, int64_t n_domains, float s_clip,
+                    int32_t* out_idx, float* out_s, float* out_o, uint8_t* out_sym, float* out_err, int fit,
+                    void* workspace, size_t ws_bytes, void* stream);
+/* The energy prune alone, for fwav_affine_all's list: local range i of [0, n) is appended to active[] (*n_active,
+ * device counter, reset first) unless fast_mode and mean(r²) < prune_thr — fwav_prune's first rule, by the same code,
+ * and none of its others (no query is read). */
+int fwav_prune_energy(const float* ranges, int64_t n, int range_size, float prune_thr, int fast_mode, int32_t* active,
+                      int32_t* n_active, void* stream);
 /* Tie check (after fwav_affine on the same rows): for every query listed in ties (fwav_sim_topk), decide whether the
  * reference's numpy tie order could change its match (fractal.py:816-824) — equal scores inside the top K when two
  * candidates of one run of equal scores both attain the minimum error; a tie at the K-th place when some member of
