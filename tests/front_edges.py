@@ -9,6 +9,9 @@ range formation (fwav_signal.hip), the domain pool and the embedding (fwav_pool_
                         frames that keep the state are long and lie everywhere.
 ``pool_signal(...)``    one signal of N_DOMAINS domains at block length bl with a denormal stretch, an overflowing
                         stretch, one inf and one NaN.
+``run_signal(...)``     runs of frames at one level each (±level samples, so a frame's energy does not depend on the
+                        summation order) — the engineered hysteresis cases of ``scan_cases()``, whose undecided runs
+                        span waves, blocks and the trips of the carry kernel (tests/golden/long_scans.npz).
 
 The builders assert on their own inputs only (never on a device's output) that the edges are what they claim."""
 import hashlib
@@ -315,3 +318,231 @@ def fp16_special_table(nd, seed=0):
     m = min(len(sp), t.size)
     t.reshape(-1)[:m] = sp[:m]
     return t
+
+
+# ---------------------------------------------------------------------------------------------- engineered runs
+# The sequential part of the hysteresis (fwav_signal.hip): a frame's state is the decision of the last decisive frame
+# before it, found by a max-scan over threads (SCAN_THREAD frames each), waves (SCAN_WAVE frames) and blocks
+# (SCAN_BLOCK frames) in k_frame_state, and over the blocks' last decisions in k_voiced_carry, one workgroup that
+# takes CARRY_TRIP blocks per loop trip, CARRY_WAVE per wave.  voiced_signal's undecided runs are a handful of frames
+# long; these signals hold runs of whole waves, blocks and trips.
+A_KEEP, A_LOUD, A_QUIET = 8.5e-3, 0.02, 1e-3    # a² between lo and hi at 1e-4 / 5e-5, above hi, below lo
+SCAN_THREAD, SCAN_WAVE, SCAN_BLOCK = 4, 256, 1024
+CARRY_WAVE, CARRY_TRIP = 64, 1024
+SCAN_WINDOWS = (5, 1)
+IN_BLOCK_P = (0, 3, 4, 255, 256, 257, 1023, 1024, 1025)
+IN_BLOCK_L = (1, 4, 255, 256, 257, 768, 1024, 2048, 3 * 1024 + 5)
+WAVE_BLOCKS = (65, 66, 130)
+TRIP_BLOCKS = (1025, 1026, 2049)
+WAVE_FRAMES = (8, 38, 64)      # the wave list runs at frames 38 (range size 19: the runtime-rs kernels) and 64 too
+DECISION_AT = 500              # a decision placed "in block b" sits at frame b·1024 + 500
+
+
+def run_signal(frame, runs, seed=0, tail=0):
+    """runs = [(level, n_frames), …] → samples ±level with seeded random signs, so that a frame's energy is level²
+    whatever the order of its sum; the last frame holds `tail` samples (0: the whole frame)."""
+    lev = np.repeat(np.array([l for l, _ in runs], F32), [n for _, n in runs])
+    nf = len(lev)
+    rng = np.random.default_rng(12000 + seed)
+    sig = np.repeat(lev, frame)
+    np.negative(sig, out=sig, where=rng.integers(0, 2, nf * frame, dtype=np.uint8).astype(bool))
+    n = nf * frame if tail == 0 else (nf - 1) * frame + tail
+    assert sig.dtype == F32 and 0 < n <= len(sig)
+    return np.ascontiguousarray(sig[:n])
+
+
+def decision_frames(window):
+    """Frames at A_QUIET or A_LOUD that make a decision: with the 5-tap smoothing one quiet frame among A_KEEP frames
+    is not decisive ((4·7.2e-5 + 1e-6)/5 > lo), three are — and one loud frame is not where the window is cut short
+    (two frames in all: (4e-4 + 7.2e-5)/5 < hi), three are; without smoothing one is, exactly where it is put."""
+    return 3 if window > 1 else 1
+
+
+class ScanCase:
+    """One engineered signal: `runs` for run_signal at `frame`, detected with `window`; `need` = the least counts of
+    scan_profile() the case is there for (asserted on the oracle's smoothed energies before a device is touched)."""
+
+    def __init__(self, name, frame, window, runs, need, seed=0, tail=0):
+        self.name, self.frame, self.window, self.runs = name, frame, window, tuple(runs)
+        self.need, self.seed, self.tail = dict(need), seed, tail
+        self.nf = sum(n for _, n in self.runs)
+
+    def signal(self):
+        return run_signal(self.frame, self.runs, self.seed, self.tail)
+
+    def __repr__(self):
+        return self.name
+
+
+def scan_claims(case):
+    """[(first frame, last frame + 1, state)] of the A_KEEP runs: the state their undecided frames must come out
+    with — that of the run before (loud: voiced, quiet or silent: unvoiced), unvoiced before any decision."""
+    out, at, state = [], 0, 0
+    for lev, n in case.runs:
+        if lev == A_KEEP:
+            out.append((at, at + n, state))
+        else:
+            state = 1 if lev > A_KEEP else 0
+        at += n
+    return out
+
+
+def scan_profile(e, hi=VOICED_THR, lo=VOICED_THR * 0.5):
+    """What the scans of a signal with smoothed frame energies `e` have to carry, in numpy:
+      decisive          frames above hi or below lo
+      carried_threads   4-frame groups without a decision, after a decision in the same 256-frame wave
+      carried_waves     whole 256-frame waves without a decision, after a decisive wave of the same block (wlast = −1)
+      undecided_blocks  1024-frame blocks without a decision (blast = −1)
+      leading_blocks    blocks that start undecided with no decision before them (carry = −1: unvoiced)
+      far_blocks        blocks that start undecided and whose last decision lies further back than the block before
+      wave_crossings    … lies in another 64-block wave of k_voiced_carry
+      trip_crossings    … lies in another 1024-block trip of k_voiced_carry's loop
+      trip_skips        … lies two or more trips back (a trip without any decision hands it on)
+    and `src`, per block the block that holds the last decision before it (−1: none)."""
+    e = np.asarray(e, F32)
+    nf = len(e)
+    dec = (e > F32(hi)) | (e < F32(lo))
+    last = np.maximum.accumulate(np.where(dec, np.arange(nf), -1))      # the last decisive frame ≤ f
+    before = np.concatenate([[-1], last[:-1]])                          # … < f
+
+    def groups(size):
+        first = np.arange(0, nf, size)
+        return first, np.add.reduceat(dec.astype(np.int64), first) == 0
+
+    tf, tnone = groups(SCAN_THREAD)
+    wf, wnone = groups(SCAN_WAVE)
+    bf, bnone = groups(SCAN_BLOCK)
+    b = np.arange(len(bf))
+    src = np.where(before[bf] >= 0, before[bf] // SCAN_BLOCK, -1)
+    used = ~dec[bf] & (src >= 0)
+    prof = dict(
+        decisive=int(dec.sum()),
+        carried_threads=int((tnone & (before[tf] >= tf // SCAN_WAVE * SCAN_WAVE) & (tf % SCAN_WAVE != 0)).sum()),
+        carried_waves=int((wnone & (before[wf] >= wf // SCAN_BLOCK * SCAN_BLOCK) & (wf % SCAN_BLOCK != 0)).sum()),
+        undecided_blocks=int(bnone.sum()),
+        leading_blocks=int((~dec[bf] & (src < 0)).sum()),
+        far_blocks=int((used & (src < b - 1)).sum()),
+        wave_crossings=int((used & (src // CARRY_WAVE < b // CARRY_WAVE)).sum()),
+        trip_crossings=int((used & (src // CARRY_TRIP < b // CARRY_TRIP)).sum()),
+        trip_skips=int((used & (b // CARRY_TRIP - src // CARRY_TRIP >= 2)).sum()))
+    return prof, src
+
+
+def in_block_cases(window):
+    """One decision at frame p, then an undecided run of L frames, p and L around a thread's 4 frames, a wave's 256
+    and the block's 1024 — voiced: A_KEEP frames (unvoiced: nothing decided yet), one loud frame, the run, which comes
+    out voiced; unvoiced: a loud block first, A_KEEP frames (voiced), the quiet decision at 1024 + p, the run, which
+    comes out unvoiced.  Then the leading run: more than two blocks with nothing decided, then a loud frame."""
+    q = decision_frames(window)
+    out = []
+    for p in IN_BLOCK_P:
+        for L in IN_BLOCK_L:
+            need = {}
+            if L >= 2 * SCAN_BLOCK:             # any 2047 consecutive frames hold a whole block
+                need["undecided_blocks"] = 1
+            if L >= 3 * SCAN_BLOCK:             # … any 3071 two in a row: the second one's carry skips the first
+                need["far_blocks"] = 1
+            lead = [(A_KEEP, p)] if p else []
+            out.append(ScanCase(f"inblock_w{window}_voiced_p{p}_L{L}", 8, window, lead + [(A_LOUD, q), (A_KEEP, L)],
+                                need, seed=len(out)))
+            out.append(ScanCase(f"inblock_w{window}_unvoiced_p{p}_L{L}", 8, window,
+                                [(A_LOUD, SCAN_BLOCK)] + lead + [(A_QUIET, q), (A_KEEP, L)], need, seed=len(out),
+                                tail=5 if L % 2 else 0))
+    # with the 5-tap smoothing frame 0 (a window of three) is below lo: a decision, so the blocks are not "leading"
+    need = dict(leading_blocks=3) if window == 1 else dict(far_blocks=1, undecided_blocks=1)
+    out.append(ScanCase(f"inblock_w{window}_leading", 8, window,
+                        [(A_KEEP, 2 * SCAN_BLOCK + 300), (A_LOUD, q), (A_KEEP, 10)], need, seed=len(out)))
+    return out
+
+
+def carry_runs(nb, decisions, window):
+    """nb blocks of A_KEEP frames with one decision per (block, "loud" | "quiet") at frame block·1024 + 500."""
+    runs, at = [], 0
+    for blk, kind in decisions:
+        f = blk * SCAN_BLOCK + DECISION_AT
+        runs.append((A_KEEP, f - at))
+        n = decision_frames(window)
+        runs.append((A_LOUD if kind == "loud" else A_QUIET, n))
+        at = f + n
+    runs.append((A_KEEP, nb * SCAN_BLOCK - at))
+    return runs
+
+
+def wave_cases(frame, window):
+    """k_voiced_carry's waves: 65, 66 and 130 blocks with the only decision in block 0, in block 63 (the last lane of
+    the carry's first wave), in block 64 (the first of its second), and a voiced decision in block 0 with an unvoiced
+    one in block 64."""
+    out = []
+    w1 = window == 1
+    for nb in WAVE_BLOCKS:
+        pats = (("only0", [(0, "loud")], dict(wave_crossings=nb - 64, far_blocks=nb - 2, undecided_blocks=nb - 2)),
+                ("only63", [(63, "loud")], dict(wave_crossings=nb - 64, undecided_blocks=nb - 3,
+                                               **(dict(leading_blocks=64) if w1 else dict(far_blocks=62)))),
+                ("only64", [(64, "loud")], dict(undecided_blocks=nb - 3,
+                                               **(dict(leading_blocks=65) if w1 else dict(wave_crossings=1)))),
+                ("v0_u64", [(0, "loud"), (64, "quiet")], dict(wave_crossings=1, far_blocks=62,
+                                                              undecided_blocks=nb - 3)))
+        for nm, decisions, need in pats:
+            out.append(ScanCase(f"wave_f{frame}_w{window}_{nb}_{nm}", frame, window, carry_runs(nb, decisions, window),
+                                need, seed=100 + len(out), tail=3 if nb % 2 else 0))
+    return out
+
+
+def trip_cases(window):
+    """k_voiced_carry's loop: 1025, 1026 and 2049 blocks (the largest 2049·1024·8 samples) with the only decision in
+    block 0; a voiced decision in block 0 and an unvoiced one in block 1023 (the last of trip 1) or 1024 (the first of
+    trip 2); the only decision, a voiced one, in block 1023 (a `running` that restarted at −1 gives the same mask as
+    an unvoiced decision, so the state handed over is the voiced one too); and, where there is a third trip (2049
+    blocks), an unvoiced decision in block 0 and a voiced one in block 700 that a decision-free trip 2 hands on to
+    trip 3."""
+    out = []
+    for nb in TRIP_BLOCKS:
+        pats = [("only0", [(0, "loud")], dict(trip_crossings=nb - 1024, **(dict(trip_skips=1) if nb > 2048 else {}))),
+                ("v0_u1023", [(0, "loud"), (1023, "quiet")], dict(trip_crossings=1, far_blocks=1021)),
+                ("v0_u1024", [(0, "loud"), (1024, "quiet")], dict(trip_crossings=1, far_blocks=1022)),
+                ("only1023", [(1023, "loud")], dict(trip_crossings=nb - 1024, undecided_blocks=nb - 3))]
+        if nb > 2 * CARRY_TRIP:
+            pats.append(("u0_v700_skip", [(0, "quiet"), (700, "loud")], dict(trip_skips=1, trip_crossings=1025)))
+        for nm, decisions, need in pats:
+            out.append(ScanCase(f"trip_w{window}_{nb}_{nm}", 8, window, carry_runs(nb, decisions, window), need,
+                                seed=200 + len(out), tail=3 if nb % 2 else 0))
+    return out
+
+
+def scan_lists():
+    """name → [ScanCase]: the in-block, wave and trip lists at frame 8 with smooth_window 5 and 1 (where a decisive
+    frame sits exactly where it is put), and the wave list at frames 38 and 64 (window 5)."""
+    out = {}
+    for w in SCAN_WINDOWS:
+        out[f"inblock_w{w}"] = in_block_cases(w)
+    for f in WAVE_FRAMES:
+        for w in (SCAN_WINDOWS if f == 8 else (5,)):
+            out[f"wave_f{f}_w{w}"] = wave_cases(f, w)
+    for w in SCAN_WINDOWS:
+        out[f"trip_w{w}"] = trip_cases(w)
+    return out
+
+
+def scan_cases():
+    return [c for lst in scan_lists().values() for c in lst]
+
+
+# through engine.compress_device (tile 1024: range size 4, frame 8, window 5): a loud start, three whole blocks of
+# A_KEEP frames and more (voiced), then silence
+PRODUCT_TILE = 1024
+PRODUCT_CASE = ScanCase("product_3_blocks_then_silence", 8, 5,
+                        [(A_LOUD, 8), (A_KEEP, 4 * SCAN_BLOCK), (0.0, SCAN_BLOCK + 90)],
+                        dict(undecided_blocks=3, far_blocks=2), seed=300, tail=3)
+
+
+def mask_runs(frame_mask):
+    """A per-frame mask as run lengths → (first value, the frames at which the value changes)."""
+    m = np.asarray(frame_mask, np.uint8)
+    return int(m[0]), np.nonzero(m[1:] != m[:-1])[0].astype(np.int64) + 1
+
+
+def mask_from_runs(first, changes, nf):
+    """… and back: u8[nf]."""
+    flips = np.zeros(nf, np.int64)
+    flips[np.asarray(changes, np.int64)] = 1
+    return ((first + np.cumsum(flips)) & 1).astype(np.uint8)

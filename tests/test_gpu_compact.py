@@ -134,6 +134,60 @@ def test_no_ranges_writes_counts_only():
     assert counts.cpu().tolist() == [0, 0]
 
 
+# k_compact_scan takes kScanThreads = 256 scan blocks (of SCAN_DOMAINS rows) per trip of its loop and hands `carry` to
+# the next trip; N_DOMAINS above ends at 16 blocks.  Range size 4 only: the largest pool here is 539 MB.
+SCAN_TRIP = 256
+LONG_N_DOMAINS = [SCAN_TRIP * SCAN_DOMAINS, SCAN_TRIP * SCAN_DOMAINS + 1, 257 * SCAN_DOMAINS + 65,
+                  513 * SCAN_DOMAINS + 7]
+
+
+def long_patterns(nd, rng):
+    """name → idx of the patterns whose kept rows lie on both sides of scan block 256 (where there is one): `anchors`
+    are a row of block 0 and one of block 255, the last block of the first trip; the random patterns get them and the
+    pool's last row too (with one row more than 256 blocks, block 256 is that row alone)."""
+    blocks = -(-nd // SCAN_DOMAINS)
+    b = np.arange(blocks)
+    every = np.minimum(b * SCAN_DOMAINS + (b * 7919) % SCAN_DOMAINS, nd - 1)
+    anchors = np.array([12345, 255 * SCAN_DOMAINS + 77])
+    w = np.arange((blocks - 2) * (SCAN_DOMAINS // 64), -(-nd // 64))  # the bitmap words of the last two scan blocks
+    return {"every_block": rng.permutation(every),
+            "one_per_word_last_two_blocks": np.concatenate([anchors, np.minimum(w * 64 + (w * 7) % 64, nd - 1)]),
+            "over": np.concatenate([patterns(nd, 100_000, rng)["over"], anchors, [nd - 1]]),
+            "negatives_in_place": np.concatenate([patterns(nd, 100_000, rng)["negatives"], anchors, [nd - 1]])}
+
+
+@pytest.mark.parametrize("nd", LONG_N_DOMAINS)
+def test_scan_carries_past_256_blocks(nd):
+    """k_compact_scan's second and third trip (n_domains of 256 scan blocks exactly — the loop's last full trip —
+    one row more, 258 blocks and 514): the same check as test_kernel_matches_restatement (numpy's unique and
+    searchsorted, guards behind every output, a dirty workspace).  Where the pool reaches past block 256, every
+    pattern here keeps rows on both sides of it — a carry that restarted at zero would number them wrongly."""
+    rs = 4
+    blocks = -(-nd // SCAN_DOMAINS)
+    assert blocks >= SCAN_TRIP and (blocks > SCAN_TRIP) == (nd > SCAN_TRIP * SCAN_DOMAINS)
+    rng = np.random.default_rng(nd)
+    try:
+        pool = _pool(nd, rs)
+        for name, idx in long_patterns(nd, rng).items():
+            kept = np.unique(idx[(idx >= 0) & (idx < nd)]) // SCAN_DOMAINS
+            assert kept.min() < SCAN_TRIP - 1 and kept.max() == blocks - 1, name
+            if blocks > SCAN_TRIP:
+                assert (kept < SCAN_TRIP).any() and (kept >= SCAN_TRIP).any(), name
+            if blocks > 2 * SCAN_TRIP:
+                assert (kept >= 2 * SCAN_TRIP).any(), name
+            m = check(idx, pool, nd, rs, in_place=name.endswith("in_place"))
+            if name == "every_block":
+                assert m == blocks
+            if name == "one_per_word_last_two_blocks":
+                assert m == 2 + -(-nd // 64) - (blocks - 2) * (SCAN_DOMAINS // 64)
+            if name == "over":
+                assert (idx >= nd).sum() >= 3
+        for name in ("first", "last", "all_negative"):
+            assert check(patterns(nd, 257, rng)[name], pool, nd, rs) == 1, name
+    finally:
+        _pool_cache.clear()
+
+
 # ------------------------------------------------------------------------------------------------ end to end
 _results: dict = {}
 

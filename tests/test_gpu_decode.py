@@ -7,7 +7,9 @@ streaming path (range_size > 32), sentinel −1 indices and constant tiles (‖T
 the same iteration count, Δ within 1e-12 relative of the oracle's f64 measure (different order from numpy's) —
 except at an iteration the exact early-exit check decided, which reports the reference's own float32 Δ.  The stop
 decision itself is always the reference's (Δ from numpy's BLAS sdot norms, fractal.py:1460-1465): the last tests
-place eps inside the certified band on both sides of the reference's Δ, single device and sharded.
+place eps inside the certified band on both sides of the reference's Δ, single device and sharded.  The last section
+runs both Δ sums past the first trip of their loops (k_decode_check above 1024 partials, k_decode_sum above 256 span
+blocks).
 """
 import numpy as np
 import pytest
@@ -40,10 +42,11 @@ def synth_matches(nr, nd, rs, seed):
 def check(idx, s, o, sym, pool, rs, **kw):
     nr = len(idx)
     rec, ran, deltas = engine.decompress_device(td(idx), td(s), td(o), td(sym), td(pool.reshape(-1)), nr, rs, **kw)
-    ref, it, rdel = O.decode(idx, s, o, sym, pool, nr, rs, **kw)
-    _, _, dref = O.decode(idx, s, o, sym, pool, nr, rs, deltas="reference", **kw)
+    ref, it, sums = O.decode(idx, s, o, sym, pool, nr, rs, deltas="sums", **kw)  # one pass, both Δ of an iteration
+    rdel, dref = [t[0] for t in sums], [t[1] for t in sums]
     assert ran == it, (ran, it)
     assert bit_equal(rec.cpu().numpy(), ref)
+    assert len(deltas) >= it
     for a, b, c in zip(deltas, rdel, dref):  # f64 measure, or the reference's own Δ where the check decided
         assert a == c or abs(a - b) <= 1e-12 * abs(b), (a, b, c)
     return ran
@@ -223,3 +226,102 @@ def test_decode_all_runs_to_the_reference_stop(side, rs):
     assert st[1] == it and st[0] == (1 if it < 40 else 0), (st, it)
     assert (it == t + 1) == (side == "stop")
     assert bit_equal(out, ref) and deltas.cpu().numpy()[t] == dref[t]
+
+
+# ------------------------------------------------------------------------------------------------ past one trip
+# k_decode_check (streaming, range_size > 32) sums one partial per k_decode_iter block of 256 ranges, 1024 threads
+# striding over them: more than 1024 · 256 ranges give a thread a second partial.  k_decode_sum (resident) strides over
+# the span blocks by 256: more than 256 · fwav_decode_span() ranges.  The sizes above stay below both.
+STREAM_TRIP = 1024 * 256
+LONG_STREAM = [STREAM_TRIP, STREAM_TRIP + 1, STREAM_TRIP + 257, 2 * STREAM_TRIP + 3]
+FORCED = dict(iterations=6, convergence_eps=0.0, s_damping=0.5)
+
+
+@pytest.mark.parametrize("rs", [33, 40])
+@pytest.mark.parametrize("nr", LONG_STREAM)
+def test_streaming_check_sums_past_1024_partials(nr, rs):
+    """Exactly 1024 partials (the last size of one trip), 1025, 1026 and 2049: six forced iterations, reconstruction
+    bit-equal and every Δ within 1e-12 of the oracle's f64 measure — a partial that a second trip dropped or read
+    twice is one part in a thousand of the sums."""
+    partials = -(-nr // 256)
+    assert partials >= 1024 and (partials > 1024) == (nr > STREAM_TRIP)
+    idx, s, o, sym, pool = synth_matches(nr, 5_000, rs, seed=rs + nr % 1000)
+    assert check(idx, s, o, sym, pool, rs, **FORCED) == 6
+
+
+def _long_stream_trace(nr, rs):
+    """The matches of one streaming case past a trip and its forced trace: per iteration (f64 Δ, reference Δ, Σ rec²,
+    Σ (next − rec)²)."""
+    m = synth_matches(nr, 5_000, rs, seed=77)
+    _, it, sums = O.decode(*m, nr, rs, deltas="sums", **FORCED)
+    assert it == 6
+    return m, sums
+
+
+def test_streaming_stop_past_one_trip_is_the_devices_decision():
+    """eps between two consecutive Δ of the forced trace, outside the certified band of both: k_decode_check's own
+    sum over 1026 partials decides (no exact check) and the loop stops where the reference's does, at iteration
+    3 to 5."""
+    from fwav import dist
+    rs, nr = 33, STREAM_TRIP + 257
+    assert -(-nr // 256) > 1024
+    (idx, s, o, sym, pool), sums = _long_stream_trace(nr, rs)
+    beta = dist.decode_beta(nr * rs)
+    t = 3
+    eps = float(np.sqrt(sums[t][0] * sums[t - 1][0]))
+    decisions = [dist.decode_decision(rr, dd, d64, eps, beta) for d64, _, rr, dd in sums]
+    assert decisions[:t + 1] == [0] * t + [1], decisions         # certain on both sides: never 2 (the exact check)
+    assert all(d[1] >= eps for d in sums[:t]) and sums[t][1] < eps  # the reference decides likewise
+    kw = dict(FORCED, convergence_eps=eps)
+    assert check(idx, s, o, sym, pool, rs, **kw) == t + 1
+    rec, ran, deltas = engine.decompress_device(td(idx), td(s), td(o), td(sym), td(pool.reshape(-1)), nr, rs, **kw)
+    assert ran == t + 1 and abs(deltas[t] - sums[t][0]) <= 1e-12 * sums[t][0] and deltas[t] != sums[t][1]
+
+
+@pytest.mark.parametrize("side", ["stop", "go_on"])
+def test_streaming_exact_check_and_resume_past_one_trip(side):
+    """eps inside the certified band, just above or below the reference's Δ of iteration 4 (as
+    test_early_exit_takes_reference_decision, on the streaming path at 1025 partials): the device stops for the exact
+    check, fwav_decode_exact decides as the reference does, and the loop resumes when it goes on."""
+    from fwav import dist
+    rs, nr = 33, STREAM_TRIP + 1
+    assert -(-nr // 256) > 1024
+    (idx, s, o, sym, pool), sums = _long_stream_trace(nr, rs)
+    beta = dist.decode_beta(nr * rs)
+    t = 3
+    d64, dref = sums[t][0], sums[t][1]
+    assert dref != d64 and all(d[0] * (1 - 2 * beta) > dref for d in sums[:t])
+    eps = dref * (1 + beta / 4) if side == "stop" else dref * (1 - beta / 4)
+    assert abs(eps - d64) < beta * d64 and dist.decode_decision(sums[t][2], sums[t][3], d64, eps, beta) == 2
+    kw = dict(iterations=8, s_damping=0.5, convergence_eps=eps)
+    ref, it, _ = O.decode(idx, s, o, sym, pool, nr, rs, **kw)
+    assert (it == t + 1) == (side == "stop") and it <= t + 2
+    rec, ran, deltas = engine.decompress_device(td(idx), td(s), td(o), td(sym), td(pool.reshape(-1)), nr, rs, **kw)
+    assert ran == it and bit_equal(rec.cpu().numpy(), ref) and deltas[t] == dref
+    for a, b in zip(deltas[:t], sums[:t]):
+        assert abs(a - b[0]) <= 1e-12 * b[0]
+
+
+def test_resident_sum_past_256_span_blocks():
+    """range_size 4 at 257 · span + 1 ranges: 258 span blocks, so k_decode_sum's threads 0 and 1 add a second
+    partial.  Six forced iterations on one device against the oracle; then the sharded sequence with
+    dist.decode_bounds(nr, 3), whose last shard writes the partials of blocks 172 … 257, and with bounds whose last
+    shard starts at block 257 (blk0 past 256): the concatenation, the iteration count and every Δ are the
+    single-device run's bit for bit."""
+    from fwav import dist
+    from fwav._lib import size_call
+    span = size_call("fwav_decode_span")
+    nr, rs = 257 * span + 1, 4
+    assert -(-nr // span) == 258 > 256
+    idx, s, o, sym, pool = synth_matches(nr, 5_000, rs, seed=258)
+    assert check(idx, s, o, sym, pool, rs, **FORCED) == 6
+    rec1, ran1, del1 = engine.decompress_device(td(idx), td(s), td(o), td(sym), td(pool.reshape(-1)), nr, rs, **FORCED)
+    thirds = dist.decode_bounds(nr, 3)
+    assert thirds[-1][0] % span == 0 and thirds[-1][0] // span <= 256 < (thirds[-1][1] - 1) // span
+    late = [(0, 100 * span), (100 * span, 257 * span), (257 * span, nr)]
+    assert late[-1][0] // span > 256
+    for bounds in (thirds, late):
+        outs = _shard_decode(idx, s, o, sym, pool, rs, bounds, FORCED["iterations"], 0.0, FORCED["s_damping"])
+        assert bit_equal(np.concatenate([r.cpu().numpy() for r, _, _ in outs]), rec1.cpu().numpy())
+        for _, ran, dl in outs:
+            assert ran == ran1 == 6 and np.array_equal(np.asarray(dl), np.asarray(del1))

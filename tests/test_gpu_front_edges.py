@@ -233,8 +233,8 @@ def test_pool_at_every_block_length(rs, step):
 
 
 # ------------------------------------------------------------------------------------------------ voiced + ranges
-def voiced_ranges(sig, frame, window, hi, lo):
-    """fwav_voiced_ranges → (ranges f32[nr, rs], mask u8[n])."""
+def voiced_ranges(sig, frame, window, hi, lo, want_mask=True):
+    """fwav_voiced_ranges → (ranges f32[nr, rs], mask u8[n]); want_mask=False passes mask_out = NULL (→ None)."""
     n = len(sig)
     rs = frame // 2
     nr = -(-n // rs)
@@ -244,14 +244,18 @@ def voiced_ranges(sig, frame, window, hi, lo):
     ranges = torch.full((nr * rs,), 7.0, dtype=torch.float32, device=dev())
     mask = torch.full((n,), 7, dtype=torch.uint8, device=dev())
     call("fwav_voiced_ranges", x.data_ptr(), n, rs, frame, window, float(F32(hi)), float(F32(lo)), ranges.data_ptr(),
-         nr, mask.data_ptr(), ws.data_ptr(), wsn, stream())
+         nr, mask.data_ptr() if want_mask else None, ws.data_ptr(), wsn, stream())
     torch.cuda.synchronize()
-    return ranges.cpu().numpy().reshape(nr, rs), mask.cpu().numpy()
+    return ranges.cpu().numpy().reshape(nr, rs), mask.cpu().numpy() if want_mask else None
 
 
-def check_voiced(sig, frame, window, hi, lo, recorded, where):
+def check_voiced(sig, frame, window, hi, lo, recorded, where, null_mask=False):
+    """null_mask: the call without a mask buffer (what engine.compress_device makes) gives the same ranges too."""
     want = O.voiced_detection(sig, frame, hi, smooth_window=window, low_threshold=lo)
     ranges, mask = voiced_ranges(sig, frame, window, hi, lo)
+    if null_mask:
+        r2, _ = voiced_ranges(sig, frame, window, hi, lo, want_mask=False)
+        assert np.array_equal(r2.view(np.uint32), ranges.view(np.uint32)), (where, "mask_out = NULL")
     if recorded is not None:
         assert np.array_equal(mask[::frame], recorded), (where, "the reference's mask")
     assert np.array_equal(mask, want), (where, np.nonzero(mask != want)[0][:8] // frame)
